@@ -12,8 +12,12 @@ With --gpus N every rank runs its own 50,000-read shard (different read seed) ag
 replicated in its GPU's HBM -- weak scaling, no collective on the data path.
 
 Prints ONE JSON line (rank 0): metric/value per the driver contract plus `roofline`
-(algorithmic 28 B per column update / live HIP-event time of the dominant kernel vs 8 TB/s HBM) and
-`cpu_baseline` (the CPU oracle, multi-threaded, on a bounded sample of the same reads).
+(algorithmic 28 B per column update / live HIP-event time of the dominant kernel vs 8 TB/s HBM).
+A plain run does only what that line needs: set up, warm up, time --steps steps, print.
+--full adds what takes runs of its own: `cpu_baseline` (the CPU oracle, multi-threaded, on a bounded
+sample of the same reads), the host stages once more and overlapped, the oracle spot check and the
+accuracy report.
+--dump-outputs DIR writes the per-read result records of the last timed step as DIR/<field>.npy (float64).
 """
 import argparse
 import json
@@ -27,6 +31,7 @@ sys.path.insert(0, ROOT)
 BYTES_PER_COLUMN_UPDATE = 28.0      # 0.25 base + 4 prev end + 4 end out + 20 VP/VN/score
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_STREAM_GBS = 5318.6             # what a streaming copy reaches on this pool (profiles/r1_hbm_stream.txt, tools/hbm_stream.hip)
+DUMP_MAX_BYTES = 60_000_000         # --dump-outputs stays under 64 MB: larger batches are dumped as a fixed sample of reads
 
 
 def _usable_cores():
@@ -49,6 +54,20 @@ def _usable_cores():
     return max(1, n)
 
 
+def dump_outputs(path, res):
+    """the per-read result records (Batch.collect(summary=True)) as one float64 array per field; a batch too large for
+    DUMP_MAX_BYTES is dumped as a seeded sample of reads, their indices in read_index.npy"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = res.dtype.names
+    if res.size * len(names) * 8 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(res.size, DUMP_MAX_BYTES // ((len(names) + 1) * 8), replace=False))
+        res = res[idx]
+        np.save(os.path.join(path, "read_index.npy"), idx.astype(np.float64))
+    for name in names:
+        np.save(os.path.join(path, name + ".npy"), res[name].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -61,16 +80,21 @@ def main():
     ap.add_argument("--bandwidth", type=int, default=35)
     ap.add_argument("--graph", choices=["linear", "bubbles", "dense"], default="linear")
     ap.add_argument("--errors", default="0.04,0.04,0.04", help="substitution,insertion,deletion rates of the read simulator")
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="reads timed through the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what takes runs of its own: CPU baseline, host stages, overlapped pipeline, "
+                                                        "oracle spot check, accuracy report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the per-read results of the last timed step as DIR/<field>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="reads timed through the CPU oracle (--full; 0 = skip)")
     ap.add_argument("--stamps", action="store_true", help="diagnostic build with per-phase cycle stamps (not a timed build)")
     ap.add_argument("--lib", default=None, help="alternative build of the library (experiments)")
-    ap.add_argument("--accuracy", type=int, default=256, help="reads scored against the simulator's true paths with the reference's criterion (CompareAlignments.cpp)")
-    ap.add_argument("--pipeline-chunks", type=int, default=12, help="chunks of the batch's size run through the overlapped host pipeline for detail.pipelined_host_to_host_Gbp_s (0 = skip)")
-    ap.add_argument("--check", type=int, default=64, help="reads compared with the oracle after the run (includes failed / later-pass reads)")
+    ap.add_argument("--accuracy", type=int, default=256, help="reads scored against the simulator's true paths with the reference's criterion (CompareAlignments.cpp; --full)")
+    ap.add_argument("--pipeline-chunks", type=int, default=12, help="chunks of the batch's size run through the overlapped host pipeline for detail.pipelined_host_to_host_Gbp_s (--full; 0 = skip)")
+    ap.add_argument("--check", type=int, default=64, help="reads compared with the oracle after the run (includes failed / later-pass reads; --full)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: ONE read set of --reads reads for the whole job, chunks pulled by the ranks from the shared queue "
                                                           "(sharding.align_queued); default is weak scaling, --reads per GPU")
     ap.add_argument("--kernel-only", action="store_true", help="time the device passes alone (profiling runs); the default step also brings the results to host memory")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -154,10 +178,12 @@ def main():
     kernel_ms, main_kernel_ms = [], []
 
     def run_steps(n, record):
+        """-> (the results of the last step, or None where the step leaves them on the device; the batch it ran)"""
+        last = None
         if args.strong and world > 1:
             for _ in range(n):
-                sharding.align_queued(graph, reads, seeds, args.bandwidth, dist=dist, chunk_reads=strong_chunk, summary=True)
-            return
+                last = sharding.align_queued(graph, reads, seeds, args.bandwidth, dist=dist, chunk_reads=strong_chunk, summary=True)
+            return last, None
         with ThreadPoolExecutor(max_workers=1) as pool:
             pending = None
             timeline = [] if (record and os.environ.get("GA_BENCH_TIMELINE")) else None
@@ -170,6 +196,7 @@ def main():
                     timeline.append(("collect", k, ta - t_base, time.perf_counter() - t_base))
                 return r
 
+            b = None
             for k in range(n):
                 b = batch if (twin is None or k % 2 == 0) else twin
                 ta = time.perf_counter()
@@ -184,17 +211,22 @@ def main():
                     pending.result()
                 pending = None if args.kernel_only else pool.submit(collect_of, b, k)
             if pending is not None:
-                pending.result()
+                last = pending.result()
             if timeline:
                 for what, k, ta, tb in sorted(timeline, key=lambda e: e[2]):
                     print("   %-8s step %d  %7.1f .. %7.1f ms" % (what, k, ta * 1e3, tb * 1e3), file=sys.stderr)
+        return last, b
 
     run_steps(args.warmup, False)
     barrier()
     t0 = time.perf_counter()
-    run_steps(args.steps, True)
+    last_out, last_batch = run_steps(args.steps, True)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        if last_out is None and last_batch is not None:
+            last_out = last_batch.collect(summary=True)        # (--kernel-only: the last step's results, still on the device)
+        dump_outputs(args.dump_outputs, last_out)
     if not kernel_ms:
         batch.run()
         sk = batch.stats()
@@ -213,7 +245,7 @@ def main():
     st = batch.stats()
     # the host stages once more on a second batch of the same reads: the first prepare / collect of a process also pay for the pinned
     # download buffer and the first touch of their arrays (the PCIe-inclusive figure in detail is the better of the two)
-    if rank == 0 and args.pipeline_chunks > 0:       # (--pipeline-chunks 0: no launches beyond the timed ones, for profiling runs)
+    if args.full and rank == 0 and args.pipeline_chunks > 0:       # (--pipeline-chunks 0: no launches beyond the timed ones, for profiling runs)
         rs2 = binding.ReadSet(reads, seeds)           # (the arrays a C caller holds; the Python lists are the simulator's)
         t0 = time.time()
         batch2 = graph.prepare(rs2, None, args.bandwidth, 0)
@@ -229,7 +261,7 @@ def main():
     # assembly of chunk k-1 on separate host threads and streams) over chunks of this batch's size.  The reads are handed over as the
     # C ABI takes them (binding.ReadSet, built outside the clock: a caller in C or C++ holds such arrays already)
     t_pipe = None
-    if rank == 0 and args.pipeline_chunks > 0:
+    if args.full and rank == 0 and args.pipeline_chunks > 0:
         from graphaligner_amd import sharding
         rs = binding.ReadSet(reads, seeds)
         t0 = time.time()
@@ -306,7 +338,7 @@ def main():
     }
 
     # ---- CPU baseline: the oracle (a port of the reference algorithm), host cores, bounded sample ----
-    if args.cpu_sample > 0 and world == 1:            # (on rank 0 of a single-GPU run only)
+    if args.full and args.cpu_sample > 0 and world == 1:            # (on rank 0 of a single-GPU run only)
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_binding as ob
         cores = _usable_cores()
@@ -320,7 +352,7 @@ def main():
                                "sample": "first %d reads of the same batch, %d threads popping reads from a shared queue (Aligner.cpp:285-298), %.1f s; 1 thread: first %d reads, %.1f s"
                                          % (n, cores, b["seconds"], n1, b1["seconds"])}
     # spot check against the oracle: a regular sample plus every read that failed or was not finished by the first pass
-    if args.check > 0 and rank == 0:
+    if args.full and args.check > 0 and rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_binding as ob
         import parity_common as pc
@@ -336,7 +368,7 @@ def main():
                 pc.compare_read(dict(d, trace=np.zeros((0, 7), dtype=np.int64)), dict(og.align(reads[i], [seeds[i]], args.bandwidth), trace=np.zeros((0, 7), dtype=np.int64)), "bench read %d" % i)
             out["detail"]["oracle_spot_check_reads"] = len(pick)
             out["detail"]["oracle_spot_check_failed_or_later_pass_reads"] = len(special)
-    if args.accuracy > 0:
+    if args.full and args.accuracy > 0:
         # node-set overlap of predicted vs true path, good when >= 0.7 (CompareAlignments.cpp:13-44, 86)
         from graphaligner_amd import compare
         k = min(args.accuracy, len(reads))

@@ -6,7 +6,7 @@ O=gpurun_out/pmc_split
 rm -rf $O && mkdir -p $O
 run() { # name, extra env, bench args
   name=$1; shift
-  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $O/$name -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --check 0 "$@" > $O/$name.json 2> $O/$name.err
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $O/$name -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --check 0 --full "$@" > $O/$name.json 2> $O/$name.err
 }
 run lin_full
 GA_DIAG_NO_TRACEBACK=1 run lin_notb
