@@ -10,9 +10,11 @@ AlignOneWay; here the whole read set is one batch on the GPU (`-t` is accepted a
 "thread" in messages and file names: everything is thread 0).  Reads are popped from the BACK of the
 list by the reference (:113-117), so with `-t 1` its output order is the reverse of the input order;
 that order is kept.  `-i` (no seeds) and `-A` (augmented graph) are not part of the hot path and
-are refused.
+are refused.  An addition of this project: `--find-seeds` (with `--seed-k K`, `--seed-max N`) stands in
+for `-s`: the seeds come from the library's k-mer index of the graph (binding.Graph.find_seeds).
 
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq -s seeds.gam -a out.gam -t 1 -b 35
+    python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq --find-seeds -a out.gam -t 1 -b 35
 """
 import getopt
 import gzip
@@ -131,32 +133,49 @@ class AlignerParams:
         self.dynamicRowStart = 64
         self.perReadFiles = True
         self.outputDir = "."
+        # --find-seeds: no seed file; the seeds come from the library's k-mer index of the graph (Graph.find_seeds)
+        self.findSeeds = False
+        self.seedK = 15
+        self.seedMax = 2
 
 
-def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr):
-    """Aligner.cpp:230-322 with the per-read loop of :107-205.  Returns the list of (read name, result dict) written."""
+def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr, seed_lib_path=None):
+    """Aligner.cpp:230-322 with the per-read loop of :107-205.  Returns the list of (read name, result dict) written.
+    (seed_lib_path: tests only.  The host emulation comes as two libraries, one that aligns and one that finds seeds; with it the
+    graph is loaded a second time into the named library for --find-seeds.  The product library does both.)"""
     if not os.path.exists(params.fastqFile):
         err.write("No fastq file exists\n")
         raise SystemExit(0)
     reads = load_reads(params.fastqFile)
     out.write("%d reads\n" % len(reads))
-    if params.seedFile == "":
+    find_seeds = getattr(params, "findSeeds", False)
+    if params.seedFile == "" and not find_seeds:
         err.write("either initial full band or seed file must be set\n")
         raise SystemExit(0)
-    if not os.path.exists(params.seedFile):
-        err.write("No seeds file exists\n")
-        raise SystemExit(0)
-    seeds_by_name = {}
-    for name, seed in binding.decode_seed_gam(open(params.seedFile, "rb").read(), lib_path=lib_path):
-        seeds_by_name.setdefault(name, []).append(seed)
+    seeds_of = {}                    # read number -> its seeds
+    if not find_seeds:
+        if not os.path.exists(params.seedFile):
+            err.write("No seeds file exists\n")
+            raise SystemExit(0)
+        seeds_by_name = {}
+        for name, seed in binding.decode_seed_gam(open(params.seedFile, "rb").read(), lib_path=lib_path):
+            seeds_by_name.setdefault(name, []).append(seed)
+        seeds_of = {i: seeds_by_name[r.seq_id] for i, r in enumerate(reads) if r.seq_id in seeds_by_name}
     graph = load_graph(params.graphFile, device=device, lib_path=lib_path)
+    if find_seeds:
+        seeder = graph if seed_lib_path is None else load_graph(params.graphFile, device=device, lib_path=seed_lib_path)
+        st = seeder.build_seed_index(k=params.seedK)
+        out.write("seed index: %d entries of %d k-mers (k %d), %.1f MB\n" % (st["entries"], st["kmers_seen"], st["k"], st["bytes"] / 1e6))
+        found = seeder.find_seeds([r.sequence for r in reads], max_seeds=params.seedMax)
+        seeds_of = {i: s for i, s in enumerate(found.seeds) if s}
+        out.write("seeds found for %d of %d reads\n" % (len(seeds_of), len(reads)))
 
     # the reference pops reads from the back of the list (Aligner.cpp:113-117)
     order = list(range(len(reads)))[::-1]
-    with_seeds = [i for i in order if reads[i].seq_id in seeds_by_name]
+    with_seeds = [i for i in order if i in seeds_of]
     results = {}
     if with_seeds:
-        batch = graph.prepare([reads[i].sequence for i in with_seeds], [seeds_by_name[reads[i].seq_id] for i in with_seeds],
+        batch = graph.prepare([reads[i].sequence for i in with_seeds], [seeds_of[i] for i in with_seeds],
                               params.initialBandwidth, params.rampBandwidth, flags=binding.GA_F_TRACE)
         batch.run()
         for i, r in zip(with_seeds, batch.collect()):
@@ -217,7 +236,7 @@ def parse_args(argv, err=sys.stderr):
     """AlignerMain.cpp:18-107"""
     p = AlignerParams()
     initial_full_band = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:")
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max="])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -239,6 +258,12 @@ def parse_args(argv, err=sys.stderr):
             p.seedFile = a
         elif o == "-d":
             p.dynamicRowStart = int(a)
+        elif o == "--find-seeds":
+            p.findSeeds = True
+        elif o == "--seed-k":
+            p.seedK = int(a)
+        elif o == "--seed-max":
+            p.seedMax = int(a)
 
     def stop(msg):
         err.write(msg + "\n")
@@ -251,8 +276,12 @@ def parse_args(argv, err=sys.stderr):
         stop("bandwidth must be >= 2")
     if p.rampBandwidth != 0 and p.rampBandwidth <= p.initialBandwidth:
         stop("backup bandwidth must be higher than initial bandwidth")
-    if not initial_full_band and p.seedFile == "":
+    if not initial_full_band and p.seedFile == "" and not p.findSeeds:
         stop("either initial full band or seed file must be set")
+    if p.findSeeds and p.seedFile != "":
+        stop("--find-seeds stands in for the seed file: give one of the two")
+    if p.findSeeds and not (11 <= p.seedK <= 31 and 1 <= p.seedMax <= 64):
+        stop("--seed-k must be 11..31 and --seed-max 1..64")
     if initial_full_band:
         stop("-i (alignment without seeds) is not part of the GPU hot path; it asserts in the reference snapshot (GraphAligner.h:1138)")
     if p.auggraphFile != "":

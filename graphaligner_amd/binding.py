@@ -60,6 +60,25 @@ class GaNamedSeed(C.Structure):
     _fields_ = [("read_name", C.c_char_p), ("seed", GaSeed)]
 
 
+class GaSeedParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("sample_shift", C.c_uint32), ("max_occ", C.c_uint32), ("max_hits", C.c_uint32), ("window", C.c_uint32),
+                ("diag_tol", C.c_uint32), ("min_support", C.c_uint32), ("max_seeds", C.c_uint32)]
+
+
+class GaSeedIndexStats(C.Structure):
+    _fields_ = [("kmers_seen", C.c_uint64), ("entries", C.c_uint64), ("distinct_keys", C.c_uint64), ("bytes", C.c_uint64),
+                ("build_ms", C.c_double), ("k", C.c_uint32), ("sample_shift", C.c_uint32)]
+
+
+class GaSeedSet(C.Structure):
+    _fields_ = [("n_reads", C.c_size_t), ("seed_offsets", C.POINTER(C.c_size_t)), ("seeds", C.POINTER(GaSeed)), ("support", C.POINTER(C.c_uint32)),
+                ("n_hits", C.POINTER(C.c_uint32)), ("truncated", C.POINTER(C.c_uint8)), ("kernel_ms", C.c_double)]
+
+
+# the seeding entry points: in the product library and in tests/_build/libga_seed_emul.so, not in the alignment-only emulation
+SEED_EXPORTS = ["ga_seed_params_default", "ga_graph_build_seed_index", "ga_graph_seed_index_stats", "ga_graph_seed_index_copy", "ga_find_seeds",
+                "ga_seed_set_free"]
+
 EXPORTS = ["ga_graph_create", "ga_graph_destroy", "ga_graph_add_node", "ga_graph_add_edge", "ga_graph_add_bigraph_node",
            "ga_graph_add_bigraph_edge", "ga_graph_finalize", "ga_graph_load_gfa", "ga_graph_upload", "ga_graph_node_count", "ga_graph_bp",
            "ga_align_batch", "ga_results_free", "ga_batch_prepare", "ga_batch_run", "ga_batch_collect", "ga_batch_free", "ga_batch_stats",
@@ -107,6 +126,15 @@ def load(path=None):
     L.ga_status_string.argtypes = [C.c_int]
     L.ga_status_string.restype = C.c_char_p
     L.ga_version.restype = C.c_char_p
+    if hasattr(L, "ga_find_seeds"):
+        L.ga_seed_params_default.argtypes = [C.c_void_p]
+        L.ga_seed_params_default.restype = None
+        L.ga_graph_build_seed_index.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.ga_graph_seed_index_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.ga_graph_seed_index_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ga_find_seeds.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.ga_seed_set_free.argtypes = [C.c_void_p]
+        L.ga_seed_set_free.restype = None
     _libs[path] = L
     return L
 
@@ -161,6 +189,76 @@ class Graph:
         b = self.prepare(reads, seeds, bw, ramp, flags)
         b.run()
         return b.collect()
+
+
+    # ---- seeds found on the device (include/graphaligner_amd.h: "seeds found on the device") ----
+    def _need_seeding(self):
+        if not hasattr(self.L, "ga_find_seeds"):
+            raise RuntimeError("this library has no seeding entry points")
+
+    def build_seed_index(self, k=15, sample_shift=2):
+        """k-mer index of this graph in HBM (replaces an earlier one); returns its statistics"""
+        self._need_seeding()
+        _check(self.L, self.L.ga_graph_build_seed_index(self.h, int(k), int(sample_shift)), "ga_graph_build_seed_index")
+        return self.seed_index_stats()
+
+    def seed_index_stats(self):
+        self._need_seeding()
+        st = GaSeedIndexStats()
+        _check(self.L, self.L.ga_graph_seed_index_stats(self.h, C.byref(st)), "ga_graph_seed_index_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def seed_index_entries(self):
+        """(keys, node indices, offsets) of the index in its order, as numpy arrays: for tests and tools"""
+        n = int(self.seed_index_stats()["entries"])
+        keys, nodes, offs = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        _check(self.L, self.L.ga_graph_seed_index_copy(self.h, keys.ctypes.data_as(C.c_void_p), nodes.ctypes.data_as(C.c_void_p),
+                                                       offs.ctypes.data_as(C.c_void_p), n), "ga_graph_seed_index_copy")
+        return keys[:n], nodes[:n], offs[:n]
+
+    def find_seeds(self, reads, **params):
+        """reads: list of str.  params: fields of ga_seed_params_t that differ from the defaults (k and sample_shift default to the index's).
+        Returns a SeedResult: .seeds = per read a list of (node, pos, reverse), as Graph.prepare / align take them, and the diagnostics."""
+        self._need_seeding()
+        p = GaSeedParams()
+        self.L.ga_seed_params_default(C.byref(p))
+        st = self.seed_index_stats()
+        p.k, p.sample_shift = st["k"], st["sample_shift"]
+        for name, v in params.items():
+            if name not in dict(GaSeedParams._fields_):
+                raise TypeError("find_seeds: unknown parameter %s" % name)
+            setattr(p, name, int(v))
+        n = len(reads)
+        keep = [r.encode() if isinstance(r, str) else r for r in reads]
+        arr = (GaRead * max(n, 1))()
+        for i, r in enumerate(keep):
+            arr[i].name = b""
+            arr[i].sequence = r
+            arr[i].length = len(r)
+        out = C.POINTER(GaSeedSet)()
+        _check(self.L, self.L.ga_find_seeds(self.h, arr, n, C.byref(p), C.byref(out)), "ga_find_seeds")
+        try:
+            S = out.contents
+            offs = np.ctypeslib.as_array(S.seed_offsets, shape=(n + 1,)).astype(np.int64) if n else np.zeros(1, dtype=np.int64)
+            total = int(offs[-1])
+            res = SeedResult()
+            flat = [(S.seeds[i].node_id, S.seeds[i].read_pos, bool(S.seeds[i].reverse)) for i in range(total)]
+            sup = [int(S.support[i]) for i in range(total)]
+            res.seeds = [flat[offs[i]:offs[i + 1]] for i in range(n)]
+            res.support = [sup[offs[i]:offs[i + 1]] for i in range(n)]
+            res.n_hits = [int(S.n_hits[i]) for i in range(n)]
+            res.truncated = [bool(S.truncated[i]) for i in range(n)]
+            res.kernel_ms = S.kernel_ms
+            return res
+        finally:
+            self.L.ga_seed_set_free(out)
+
+
+class SeedResult:
+    """what Graph.find_seeds returns: seeds[i] = [(node, pos, reverse), ...] of read i (best first, possibly empty), support[i] the
+    seeds' support, n_hits[i] / truncated[i] the read's hit count and whether it was cut at max_hits, kernel_ms the kernel's time"""
+    seeds = support = n_hits = truncated = None
+    kernel_ms = 0.0
 
 
 class ReadSet:

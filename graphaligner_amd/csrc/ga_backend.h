@@ -78,10 +78,34 @@ struct GaEqSource
 	uint8_t padCode = 0;
 };
 
+// ---- seeding (ga_seed.h): a k-mer index of the uploaded graph and, per batch of reads, the seeds it gives ------------------------
+struct GaSeedIndexInfo { uint64_t kmers_seen = 0, entries = 0, distinct_keys = 0, bytes = 0; double build_ms = 0; uint32_t k = 0, sample_shift = 0, dir_bits = 0; };
+// per read r: n_seeds[r] seeds at [r * max_seeds ..): node INDEX, read position and support of each; the number of hits used; truncated
+struct GaSeedOut
+{
+	std::vector<uint32_t> n_seeds, n_hits, truncated;
+	std::vector<uint32_t> node, pos, support;
+	double kernel_ms = 0;
+};
+class GaSeedEngine
+{
+public:
+	virtual ~GaSeedEngine() {}
+	// linx[node] = 2 * lin + strand flag (include/graphaligner_amd.h: the linear coordinate); one per node, dummy nodes included
+	virtual int build(uint32_t k, uint32_t sampleShift, const std::vector<int64_t>& linx) = 0;
+	virtual bool built() const = 0;
+	virtual GaSeedIndexInfo info() const = 0;
+	virtual int copy(uint64_t* keys, uint32_t* nodes, uint32_t* offsets, size_t capacity) const = 0;
+	// reads: seqs[i] of lens[i] characters
+	virtual int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) = 0;
+};
+
 class GaBackendGraph
 {
 public:
 	virtual ~GaBackendGraph() {}
+	// nullptr: this back end has no seeding (the alignment-only host emulation of tests/emul)
+	virtual GaSeedEngine* seedEngine() { return nullptr; }
 	// true: ga_backend_create_batch wants a GaEqSource and builds the match words on its side (the product: a kernel over the uploaded
 	// reads); false: it wants the finished words (the host emulation of tests/emul)
 	virtual bool buildsMatchWords() const { return false; }
@@ -108,6 +132,11 @@ public:
 	virtual void fetchDone() {}
 	virtual GaRunStats stats() const = 0;
 };
+
+// what the seeding entry points (ga_seed_host.cpp) need of a graph, which is ga_host.cpp's own
+struct ga_graph;
+struct GaGraphView { bool finalized; const std::vector<int64_t>* ids; const GaFlatGraph* flat; GaBackendGraph* device; };
+GaGraphView ga_graph_view(const ga_graph* g);
 
 // returns nullptr + sets *status (GA_E_NO_DEVICE ...) on failure
 GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& g, const GaHmmTables& hmm, int device, int* status);

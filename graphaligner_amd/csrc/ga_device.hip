@@ -17,6 +17,7 @@
 #include "ga_backend.h"
 #include "ga_kernel.h"
 #include "ga_lanes.h"
+#include "ga_seed_dev.h"
 
 namespace {
 
@@ -237,6 +238,10 @@ struct DevGraph : GaBackendGraph
 			if (pool->idle.size() < 6) pool->idle.emplace_back(cap, q); else hipHostFree(q);
 		});
 	}
+
+	// seeding (ga_seed.h): the k-mer index of this graph and its buffers, built on request
+	std::unique_ptr<gasd::DevSeedEngine> seed;
+	GaSeedEngine* seedEngine() override { return seed.get(); }
 
 	int device = 0;
 	GaDevGraph g;
@@ -807,6 +812,7 @@ GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& flat, const GaHmmTabl
 	bad |= g->put(h, &dh);
 	g->hmm = const_cast<GaHmmTables*>(dh);
 	if (bad) { delete g; *status = GA_E_DEVICE; return nullptr; }
+	g->seed = std::make_unique<gasd::DevSeedEngine>(g, device, g->cus, g->g);
 	*status = 0;
 	return g;
 }

@@ -134,6 +134,8 @@ struct ga_graph
 	}
 };
 
+GaGraphView ga_graph_view(const ga_graph* g) { return GaGraphView{g->finalized, &g->ids, &g->flat, g->device}; }
+
 static int addNode(ga_graph* g, int64_t id, const char* seq, size_t len, bool rev)
 {
 	if (g->finalized) return GA_E_INVALID;

@@ -1,0 +1,326 @@
+// ga_seed.h -- seeds found on the device: the k-mer index of the uploaded graph and, per read, the lookup of its k-mers and the
+// ranking of the hits (include/graphaligner_amd.h states the rule; DESIGN.md section 10 argues it).
+//
+// One wave (= one workgroup of 64 lanes) works on one read at a time.  The program is written in PHASES: inside GAS_LANES(l) { ... }
+// every lane runs the block for its own l, and lanes exchange values only through the SeedLds block (LDS) or the wave's hit buffer
+// (HBM) with a wave_sync() between the phase that writes and the phase that reads; everything declared outside a lane block is the
+// same in every lane (it is derived from such exchanged values), so the control flow around the blocks is uniform.  On gfx950 a lane
+// block is straight-line code of the lane; in the host build of the tests (tests/emul_seed) it is a loop over the 64 lanes, which is
+// the same program because of that discipline.  The one wave primitive that is not a lane block is the exclusive scan of the tile's
+// hit counts (cross-lane DPP/permute moves on the device, a running sum on the host).
+//
+// LIMITS: a k-mer lies inside one node (k-mers across an edge are not indexed; nodes shorter than k contribute nothing).
+#pragma once
+#include "ga_types.h"
+#ifndef GA_WAVE_HEADER
+#define GA_WAVE_HEADER "ga_wave.h"
+#endif
+#include GA_WAVE_HEADER
+
+namespace gas {
+
+#ifdef GA_EMULATE
+#define GAS_FN inline
+#define GAS_LANES(l) for (int l = 0; l < 64; l++)
+#else
+#define GAS_FN __device__ __forceinline__
+#define GAS_LANES(l) if (const int l = (int)threadIdx.x; true)
+#endif
+
+constexpr uint32_t kMinArm = 193;          // a direction shorter than this asserts in the reference's engine (GraphAligner.h:906)
+constexpr uint32_t kSeg = 4096;            // read positions whose bases are held 2 bits each in LDS at a time
+constexpr uint32_t kSegWords = kSeg / 16 + 2;   // + the k - 1 <= 30 bases behind the segment's last position (a key spans up to three words)
+
+struct SeedIndex
+{
+	uint32_t k, sample_shift;
+	uint32_t dir_shift;                    // bucket of a key = key >> dir_shift (its top bits)
+	uint32_t n_entries;
+	const uint64_t* keys;                  // [n_entries] ascending; equal keys in (node, offset) order
+	const uint64_t* vals;                  // [n_entries] node index << 32 | offset
+	const uint32_t* dir;                   // [buckets + 1] first entry of each bucket
+	const int64_t* linx;                   // [n_nodes] 2 * linear coordinate of the node's first base + strand flag
+};
+
+struct SeedRead { uint64_t off; uint32_t len, reserved; };      // off: multiple of 16; at least 16 bytes of padding follow the read
+
+struct SeedLaunch
+{
+	SeedIndex ix;
+	GaSeedParams p;
+	const uint8_t* seq;
+	const SeedRead* reads;
+	const uint32_t* order;                 // read numbers, longest read first
+	uint32_t n_reads, reserved;
+	// per wave slot, max_hits entries each: read position, node index, 2 * diag + strand, support (0: not a candidate)
+	uint32_t* hit_p; uint32_t* hit_node; int64_t* hit_dx; uint32_t* hit_sup;
+	uint32_t* out_n;                       // [n_reads][3] seeds, hits used, truncated
+	uint32_t* out_seed;                    // [n_reads][max_seeds][3] node index, read position, support
+};
+
+struct SeedLds
+{
+	uint32_t code[kSegWords + 1], inval[kSegWords + 1];    // 16 bases / 16 "not ACGT" flags per word, first base in the top bits
+	uint32_t cnt[64], tot;
+	uint32_t bestSup[64], bestIdx[64];
+	int64_t taken[64];                                     // 2 * diag + strand of the seeds taken so far
+};
+
+GAS_FN uint32_t mix64(uint64_t x) { x ^= x >> 29; x *= 0x9e3779b97f4a7c15ull; x ^= x >> 32; return (uint32_t)x; }
+GAS_FN bool kept(uint64_t key, uint32_t sampleShift) { return (mix64(key) & ((1u << sampleShift) - 1u)) == 0; }
+GAS_FN int64_t absdiff(int64_t a, int64_t b) { return a < b ? b - a : a - b; }
+
+// ---- index build ---------------------------------------------------------------------------------------------------------------
+// the kept k-mers of one node in offset order (the key rolls along the node: one base per step); returns their number
+template <class F> GAS_FN uint64_t node_kmers(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t sampleShift, F emit)
+{
+	if (node == 0 || node + 1 >= g.n_nodes) return 0;                    // the two dummy nodes
+	const uint64_t start = g.node_start[node], len = g.node_start[node + 1] - start;
+	if (len < k) return 0;
+	const uint64_t mask = (1ull << (2 * k)) - 1;
+	uint64_t key = 0, n = 0;
+	uint32_t w = g.seq2[start >> 4];
+	for (uint64_t i = 0; i < len; i++)
+	{
+		const uint64_t col = start + i;
+		if ((col & 15) == 0) w = g.seq2[col >> 4];
+		key = ((key << 2) | ((w >> ((col & 15) * 2)) & 3u)) & mask;
+		if (i + 1 >= k && kept(key, sampleShift)) { emit(key, (uint32_t)(i + 1 - k)); n++; }
+	}
+	return n;
+}
+GAS_FN void index_count(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t sampleShift, uint64_t* counts)
+{
+	counts[node] = node_kmers(g, node, k, sampleShift, [](uint64_t, uint32_t) {});
+}
+GAS_FN void index_write(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t sampleShift, const uint64_t* firstEntry, uint64_t* keys, uint64_t* vals)
+{
+	uint64_t at = firstEntry[node];
+	node_kmers(g, node, k, sampleShift, [&](uint64_t key, uint32_t o) { keys[at] = key; vals[at] = ((uint64_t)node << 32) | o; at++; });
+}
+// entry i (i = n: the end) names itself as the first entry of every bucket between its predecessor's and its own
+GAS_FN void index_dir(const uint64_t* keys, uint32_t n, uint32_t dirShift, uint32_t buckets, uint32_t* dir, uint32_t i)
+{
+	const uint64_t lo = i == 0 ? 0 : (keys[i - 1] >> dirShift) + 1;
+	const uint64_t hi = i == n ? buckets : (keys[i] >> dirShift);
+	for (uint64_t b = lo; b <= hi; b++) dir[b] = i;
+}
+
+// ---- lookup --------------------------------------------------------------------------------------------------------------------
+// entries of `key`: one directory load, a search inside the bucket (about one entry per bucket by the choice of dir_shift), then a
+// walk over at most maxOcc + 1 equal keys
+GAS_FN uint32_t lookup(const SeedIndex& ix, uint64_t key, uint32_t maxOcc, uint32_t& first)
+{
+	const uint64_t b = key >> ix.dir_shift;
+	uint32_t lo = ix.dir[b];
+	const uint32_t end = ix.dir[b + 1];
+	first = lo;
+	if (end > ix.n_entries || lo > end) return 0;                          // (never with a directory built by index_dir: keeps every loop here bounded)
+	uint32_t hi = end;
+	while (hi - lo > 4) { const uint32_t mid = lo + ((hi - lo) >> 1); if (ix.keys[mid] < key) lo = mid + 1; else hi = mid; }
+	while (lo < end && ix.keys[lo] < key) lo++;
+	uint32_t occ = 0;
+	while (lo + occ < end && occ <= maxOcc && ix.keys[lo + occ] == key) occ++;
+	first = lo;
+	return occ;
+}
+
+// exclusive scan of lds.cnt over the lanes, total into lds.tot (the caller syncs before and after)
+GAS_FN void scan_counts(SeedLds& lds)
+{
+#ifdef GA_EMULATE
+	uint32_t run = 0;
+	for (int l = 0; l < 64; l++) { const uint32_t c = lds.cnt[l]; lds.cnt[l] = run; run += c; }
+	lds.tot = run;
+#else
+	const int l = (int)threadIdx.x;
+	const uint32_t own = lds.cnt[l];
+	uint32_t v = own;
+	for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64); if (l >= d) v += o; }
+	lds.cnt[l] = v - own;
+	if (l == 63) lds.tot = v;
+#endif
+}
+
+// sixteen characters -> their 2-bit codes and "not one of ACGT" flags, first character in the top bits
+GAS_FN void pack16(const uint8_t* p, uint32_t nValid, uint32_t& code, uint32_t& inval)
+{
+	code = 0; inval = 0xffffu;
+	if (nValid == 0) return;
+	const uint32_t* q = (const uint32_t*)p;                                // (16-byte aligned, padded: SeedRead)
+	const uint32_t w[4] = {q[0], q[1], q[2], q[3]};
+#pragma unroll
+	for (uint32_t i = 0; i < 16; i++)
+	{
+		const uint32_t c = (w[i >> 2] >> ((i & 3) * 8)) & 0xffu;
+		const bool ok = i < nValid && (c == 'A' || c == 'C' || c == 'G' || c == 'T');
+		if (ok) { code |= (((c >> 1) ^ (c >> 2)) & 3u) << (30 - 2 * i); inval &= ~(1u << (15 - i)); }
+	}
+}
+
+// one read: its hits into the wave's hit buffer, their support, the greedy choice
+GAS_FN void seed_read(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t read)
+{
+	const SeedIndex& ix = L.ix;
+	const GaSeedParams& P = L.p;
+	const SeedRead rd = L.reads[read];
+	const uint8_t* seq = L.seq + rd.off;
+	const uint32_t len = rd.len, k = ix.k;
+	uint32_t* hitP = L.hit_p + (uint64_t)slot * P.max_hits;
+	uint32_t* hitNode = L.hit_node + (uint64_t)slot * P.max_hits;
+	int64_t* hitDx = L.hit_dx + (uint64_t)slot * P.max_hits;
+	uint32_t* hitSup = L.hit_sup + (uint64_t)slot * P.max_hits;
+	const uint32_t nPos = len >= k ? len - k + 1 : 0;                      // read positions that start a k-mer
+	uint32_t total = 0;
+	bool truncated = false;
+
+	for (uint32_t s0 = 0; s0 < nPos && !truncated; s0 += kSeg)
+	{
+		gaw::wave_sync();                                                    // (the previous segment's words are no longer read)
+		GAS_LANES(l)
+		{
+			for (uint32_t w = (uint32_t)l; w < kSegWords + 1; w += 64)
+			{
+				const uint64_t at = (uint64_t)s0 + 16ull * w;
+				uint32_t c, iv;
+				pack16(seq + at, at < len ? (len - at < 16 ? (uint32_t)(len - at) : 16u) : 0u, c, iv);
+				lds.code[w] = c; lds.inval[w] = iv;
+			}
+		}
+		gaw::wave_sync();
+		for (uint32_t t0 = 0; t0 < kSeg && s0 + t0 < nPos && !truncated; t0 += 64)
+		{
+			GAS_LANES(l)
+			{
+				const uint32_t q = t0 + (uint32_t)l, p = s0 + q;
+				uint32_t c = 0;
+				if (p < nPos)
+				{
+					const uint32_t j = q >> 4, sh = q & 15;
+					const uint64_t iv = ((uint64_t)lds.inval[j] << 32) | ((uint64_t)lds.inval[j + 1] << 16) | lds.inval[j + 2];
+					const bool bad = (((iv << sh) & 0xffffffffffffull) >> (48 - k)) != 0;
+					const uint64_t hi = ((uint64_t)lds.code[j] << 32) | lds.code[j + 1];
+					const uint64_t x = sh ? (hi << (2 * sh)) | ((uint64_t)lds.code[j + 2] >> (32 - 2 * sh)) : hi;
+					const uint64_t key = x >> (64 - 2 * k);
+					if (!bad && kept(key, ix.sample_shift))                      // (the kept test comes before any index access)
+					{
+						uint32_t first;
+						const uint32_t occ = lookup(ix, key, P.max_occ, first);
+						if (occ >= 1 && occ <= P.max_occ) { c = occ; lds.bestIdx[l] = first; }
+					}
+				}
+				lds.cnt[l] = c;
+			}
+			gaw::wave_sync();
+			scan_counts(lds);
+			gaw::wave_sync();
+			GAS_LANES(l)
+			{
+				// hits leave in (p, index order) order: lane order is position order, a lane's entries are in index order
+				const uint32_t p = s0 + t0 + (uint32_t)l;
+				const uint32_t n = (l == 63 ? lds.tot : lds.cnt[l + 1]) - lds.cnt[l];
+				const uint32_t first = lds.bestIdx[l];
+				for (uint32_t e = 0; e < n; e++)
+				{
+					const uint32_t at = total + lds.cnt[l] + e;
+					if (at >= P.max_hits) break;
+					const uint64_t v = ix.vals[first + e];
+					const uint32_t node = (uint32_t)(v >> 32);
+					const int64_t lx = ix.linx[node];
+					const int64_t diag = (lx >> 1) + (int64_t)(uint32_t)v - (int64_t)p;
+					hitP[at] = p; hitNode[at] = node; hitDx[at] = diag * 2 + (lx & 1);
+				}
+			}
+			total += lds.tot;
+			if (total > P.max_hits) { total = P.max_hits; truncated = true; }
+			gaw::wave_sync();                                                // (lds.tot is read before the next tile writes it)
+		}
+	}
+	gaw::wave_sync();                                                        // the hit buffer is complete and visible to every lane
+
+	// support: hits are in p order, so the hits within `window` of one are a run around it.  Its two ends come from binary searches;
+	// the count over the run then has no exit that depends on a loaded value, so its loads are in flight together (a walk outwards
+	// that stops at the first hit outside the window waits for every load in turn: 18.1 ms against 13.6 ms for the benchmark's batch)
+	const uint32_t H = total;
+	GAS_LANES(l)
+	{
+		for (uint32_t i = (uint32_t)l; i < H; i += 64)
+		{
+			const uint32_t p = hitP[i];
+			const int64_t dx = hitDx[i];
+			uint32_t lo = 0, hi = i;
+			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (p - hitP[mid] > P.window) lo = mid + 1; else hi = mid; }
+			const uint32_t from = lo;
+			lo = i + 1; hi = H;
+			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (hitP[mid] - p <= P.window) lo = mid + 1; else hi = mid; }
+			uint32_t sup = 0;
+#pragma unroll 4
+			for (uint32_t j = from; j < lo; j++)
+			{
+				const int64_t o = hitDx[j];
+				sup += (((o ^ dx) & 1) == 0 && absdiff(o >> 1, dx >> 1) <= (int64_t)P.diag_tol) ? 1u : 0u;       // (j = i counts: the hit itself)
+			}
+			const bool cand = p >= kMinArm && len - p >= kMinArm && sup >= P.min_support;
+			hitSup[i] = cand ? sup : 0u;
+		}
+	}
+	gaw::wave_sync();
+
+	// the choice: per round every lane names its best remaining candidate (highest support, then lowest hit number = (p, node, offset)
+	// order), the wave takes the best of those
+	uint32_t nSeeds = 0;
+	for (uint32_t r = 0; r < P.max_seeds; r++)
+	{
+		GAS_LANES(l)
+		{
+			uint32_t bs = 0, bi = 0xffffffffu;
+			for (uint32_t i = (uint32_t)l; i < H; i += 64)
+			{
+				const uint32_t s = hitSup[i];
+				if (s <= bs) continue;
+				const int64_t dx = hitDx[i];
+				bool same = false;
+				for (uint32_t t = 0; t < r; t++)
+				{
+					const int64_t o = lds.taken[t];
+					if (((o ^ dx) & 1) == 0 && absdiff(o >> 1, dx >> 1) <= (int64_t)P.diag_tol) same = true;
+				}
+				if (!same) { bs = s; bi = i; }
+			}
+			lds.bestSup[l] = bs; lds.bestIdx[l] = bi;
+		}
+		gaw::wave_sync();
+		uint32_t bs = 0, bi = 0xffffffffu;
+		for (int l = 0; l < 64; l++)
+		{
+			const uint32_t s = lds.bestSup[l], i = lds.bestIdx[l];
+			if (s > bs || (s == bs && s != 0 && i < bi)) { bs = s; bi = i; }
+		}
+		gaw::wave_sync();                                                    // (everyone has read the round's table)
+		if (bs == 0) break;
+		GAS_LANES(l)
+		{
+			if (l == 0)
+			{
+				lds.taken[r] = hitDx[bi];
+				uint32_t* o = L.out_seed + ((uint64_t)read * P.max_seeds + r) * 3;
+				o[0] = hitNode[bi]; o[1] = hitP[bi]; o[2] = bs;
+			}
+		}
+		nSeeds++;
+		gaw::wave_sync();
+	}
+	GAS_LANES(l)
+	{
+		if (l == 0) { uint32_t* o = L.out_n + (uint64_t)read * 3; o[0] = nSeeds; o[1] = H; o[2] = truncated ? 1u : 0u; }
+	}
+}
+
+// a wave: the reads are dealt longest first, round-robin over the waves (read number slot, slot + slots, ... of that order), so every
+// wave gets the same mix of lengths and the hand-out needs no counter: the loop is the same in every lane by construction
+GAS_FN void seed_wave(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t slots)
+{
+	for (uint32_t at = slot; at < L.n_reads; at += slots) seed_read(L, lds, slot, L.order[at]);
+}
+
+}  // namespace gas

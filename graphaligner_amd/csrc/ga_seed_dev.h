@@ -1,0 +1,240 @@
+// ga_seed_dev.h -- the gfx950 side of seeding: the kernels around the program of ga_seed.h and the engine that owns the index in HBM.
+// Included by ga_device.hip only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "ga_backend.h"
+#include "ga_seed.h"
+
+namespace gasd {
+
+#define GAS_HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fprintf(stderr, "graphaligner_amd: %s failed: %s\n", #call, hipGetErrorString(e_)); return 102; } } while (0)
+
+// index build, once per graph: one lane per node (a node's k-mers must leave in offset order, and the key rolls along the node)
+__global__ void __launch_bounds__(256) ga_seed_count_kernel(GaDevGraph g, uint32_t k, uint32_t sampleShift, uint64_t* counts)
+{
+	const uint32_t node = blockIdx.x * 256u + threadIdx.x;
+	if (node < g.n_nodes) gas::index_count(g, node, k, sampleShift, counts);
+	else if (node == g.n_nodes) counts[node] = 0;                         // (the scan's last element = the total)
+}
+__global__ void __launch_bounds__(256) ga_seed_write_kernel(GaDevGraph g, uint32_t k, uint32_t sampleShift, const uint64_t* firstEntry, uint64_t* keys, uint64_t* vals)
+{
+	const uint32_t node = blockIdx.x * 256u + threadIdx.x;
+	if (node < g.n_nodes) gas::index_write(g, node, k, sampleShift, firstEntry, keys, vals);
+}
+__global__ void __launch_bounds__(256) ga_seed_dir_kernel(const uint64_t* keys, uint32_t n, uint32_t dirShift, uint32_t buckets, uint32_t* dir, unsigned long long* distinct)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i > n) return;
+	gas::index_dir(keys, n, dirShift, buckets, dir, (uint32_t)i);
+	const bool isNew = i < n && (i == 0 || keys[i] != keys[i - 1]);
+	const uint64_t m = __ballot(isNew);
+	if (m != 0 && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(distinct, (unsigned long long)__builtin_popcountll(m));
+}
+// the hot path: one wave per read at a time
+__global__ void __launch_bounds__(64) ga_seed_find_kernel(gas::SeedLaunch L)
+{
+	__shared__ gas::SeedLds lds;
+	gas::seed_wave(L, lds, blockIdx.x, gridDim.x);
+}
+
+constexpr size_t kWavesPerCu = 16;
+
+struct DevSeedEngine : GaSeedEngine
+{
+	GaBackendGraph* owner;
+	int device;
+	int cus;
+	GaDevGraph g;
+	std::mutex lock;                           // one build or find at a time per graph
+	gas::SeedIndex ix{};
+	GaSeedIndexInfo inf;
+	bool have = false;
+	void* dKeys = nullptr; void* dVals = nullptr; void* dDir = nullptr; void* dLinx = nullptr;
+	// buffers of find(), kept between calls
+	void* work = nullptr; size_t workBytes = 0;
+	void* hits = nullptr; size_t hitsBytes = 0;
+	hipEvent_t evA = nullptr, evB = nullptr;
+
+	DevSeedEngine(GaBackendGraph* o, int dev, int nCus, const GaDevGraph& graph) : owner(o), device(dev), cus(nCus), g(graph) {}
+	void dropIndex()
+	{
+		for (void** p : {&dKeys, &dVals, &dDir, &dLinx}) { if (*p) hipFree(*p); *p = nullptr; }
+		have = false;
+	}
+	~DevSeedEngine() override
+	{
+		hipSetDevice(device);
+		dropIndex();
+		if (work) hipFree(work);
+		if (hits) hipFree(hits);
+		if (evA) hipEventDestroy(evA);
+		if (evB) hipEventDestroy(evB);
+	}
+	bool built() const override { return have; }
+	GaSeedIndexInfo info() const override { return inf; }
+
+	int build(uint32_t k, uint32_t sampleShift, const std::vector<int64_t>& linx) override
+	{
+		std::lock_guard<std::mutex> guard(lock);
+		GAS_HIP_OK(hipSetDevice(device));
+		dropIndex();
+		const auto t0 = std::chrono::steady_clock::now();
+		const uint32_t nNodes = g.n_nodes;
+		const uint32_t blocks = (nNodes + 1 + 255) / 256;
+		uint64_t* counts = nullptr; uint64_t* firstEntry = nullptr;
+		void* tmp = nullptr; uint64_t* keysIn = nullptr; uint64_t* valsIn = nullptr;
+		auto cleanup = [&]() { for (void* p : {(void*)counts, (void*)firstEntry, tmp, (void*)keysIn, (void*)valsIn}) if (p) hipFree(p); };
+#define GAS_TRY(call) do { if ((call) != hipSuccess) { fprintf(stderr, "graphaligner_amd: %s failed\n", #call); cleanup(); dropIndex(); return 102; } } while (0)
+		GAS_TRY(hipMalloc((void**)&counts, ((size_t)nNodes + 1) * 8));
+		GAS_TRY(hipMalloc((void**)&firstEntry, ((size_t)nNodes + 1) * 8));
+		hipLaunchKernelGGL(ga_seed_count_kernel, dim3(blocks), dim3(256), 0, 0, g, k, sampleShift, counts);
+		size_t tmpBytes = 0;
+		GAS_TRY(rocprim::exclusive_scan(nullptr, tmpBytes, counts, firstEntry, (uint64_t)0, (size_t)nNodes + 1, rocprim::plus<uint64_t>()));
+		GAS_TRY(hipMalloc(&tmp, std::max<size_t>(tmpBytes, 16)));
+		GAS_TRY(rocprim::exclusive_scan(tmp, tmpBytes, counts, firstEntry, (uint64_t)0, (size_t)nNodes + 1, rocprim::plus<uint64_t>()));
+		uint64_t total = 0;
+		GAS_TRY(hipMemcpy(&total, firstEntry + nNodes, 8, hipMemcpyDeviceToHost));
+		hipFree(tmp); tmp = nullptr;
+		if (total >= 0xfffffff0ull) { cleanup(); return 100; }             // entry numbers are 32-bit
+		const uint32_t n = (uint32_t)total;
+		const size_t cap = std::max<size_t>(n, 2);
+		GAS_TRY(hipMalloc((void**)&keysIn, cap * 8));
+		GAS_TRY(hipMalloc((void**)&valsIn, cap * 8));
+		GAS_TRY(hipMalloc(&dKeys, cap * 8));
+		GAS_TRY(hipMalloc(&dVals, cap * 8));
+		hipLaunchKernelGGL(ga_seed_write_kernel, dim3(blocks), dim3(256), 0, 0, g, k, sampleShift, firstEntry, keysIn, valsIn);
+		// by key, stable: equal keys keep the (node, offset) order they were written in
+		if (n > 0)
+		{
+			tmpBytes = 0;
+			GAS_TRY(rocprim::radix_sort_pairs(nullptr, tmpBytes, keysIn, (uint64_t*)dKeys, valsIn, (uint64_t*)dVals, (size_t)n, 0u, 2u * k));
+			GAS_TRY(hipMalloc(&tmp, std::max<size_t>(tmpBytes, 16)));
+			GAS_TRY(rocprim::radix_sort_pairs(tmp, tmpBytes, keysIn, (uint64_t*)dKeys, valsIn, (uint64_t*)dVals, (size_t)n, 0u, 2u * k));
+		}
+		// the directory: top bits of the key -> first entry; about one entry per bucket
+		uint32_t bits = 1;
+		while (bits < 2 * k && bits < 28 && (1ull << bits) < n) bits++;
+		const uint32_t buckets = 1u << bits;
+		unsigned long long* dDistinct = nullptr;
+		GAS_TRY(hipMalloc(&dDir, ((size_t)buckets + 2) * 4));
+		GAS_TRY(hipMalloc(&dLinx, std::max<size_t>(linx.size(), 1) * 8));
+		GAS_TRY(hipMemcpy(dLinx, linx.data(), linx.size() * 8, hipMemcpyHostToDevice));
+		dDistinct = (unsigned long long*)counts;                            // (reused: the counts are no longer needed)
+		GAS_TRY(hipMemset(dDistinct, 0, 8));
+		hipLaunchKernelGGL(ga_seed_dir_kernel, dim3((uint32_t)(((uint64_t)n + 1 + 255) / 256)), dim3(256), 0, 0, (const uint64_t*)dKeys, n, 2 * k - bits, buckets, (uint32_t*)dDir, dDistinct);
+		unsigned long long distinct = 0;
+		GAS_TRY(hipMemcpy(&distinct, dDistinct, 8, hipMemcpyDeviceToHost));
+		GAS_TRY(hipDeviceSynchronize());
+#undef GAS_TRY
+		cleanup();
+		ix.k = k; ix.sample_shift = sampleShift; ix.dir_shift = 2 * k - bits; ix.n_entries = n;
+		ix.keys = (const uint64_t*)dKeys; ix.vals = (const uint64_t*)dVals; ix.dir = (const uint32_t*)dDir; ix.linx = (const int64_t*)dLinx;
+		inf = GaSeedIndexInfo();
+		inf.entries = n; inf.distinct_keys = distinct; inf.k = k; inf.sample_shift = sampleShift; inf.dir_bits = bits;
+		inf.bytes = (uint64_t)n * 16 + ((uint64_t)buckets + 1) * 4 + (uint64_t)linx.size() * 8;
+		inf.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		have = true;
+		return 0;
+	}
+
+	int copy(uint64_t* keys, uint32_t* nodes, uint32_t* offsets, size_t capacity) const override
+	{
+		if (!have) return 100;
+		const size_t n = std::min<size_t>(capacity, ix.n_entries);
+		if (n == 0) return 0;
+		GAS_HIP_OK(hipSetDevice(device));
+		std::vector<uint64_t> vals(n);
+		GAS_HIP_OK(hipMemcpy(keys, dKeys, n * 8, hipMemcpyDeviceToHost));
+		GAS_HIP_OK(hipMemcpy(vals.data(), dVals, n * 8, hipMemcpyDeviceToHost));
+		for (size_t i = 0; i < n; i++) { nodes[i] = (uint32_t)(vals[i] >> 32); offsets[i] = (uint32_t)vals[i]; }
+		return 0;
+	}
+
+	int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override
+	{
+		std::lock_guard<std::mutex> guard(lock);
+		if (!have) return 100;
+		out.n_seeds.assign(nReads, 0); out.n_hits.assign(nReads, 0); out.truncated.assign(nReads, 0);
+		out.node.assign(nReads * p.max_seeds, 0); out.pos.assign(nReads * p.max_seeds, 0); out.support.assign(nReads * p.max_seeds, 0);
+		out.kernel_ms = 0;
+		if (nReads == 0) return 0;
+		GAS_HIP_OK(hipSetDevice(device));
+		// the batch: characters (every read at a multiple of 16 with 16 bytes of padding behind it), read records, the hand-out order
+		std::vector<gas::SeedRead> recs(nReads);
+		uint64_t seqBytes = 0;
+		for (size_t i = 0; i < nReads; i++)
+		{
+			if (lens[i] > 0xfffffff0ull) return 100;
+			recs[i] = gas::SeedRead{seqBytes, (uint32_t)lens[i], 0};
+			seqBytes += ((lens[i] + 15) & ~(size_t)15) + 16;
+		}
+		std::vector<uint32_t> order(nReads);
+		for (size_t i = 0; i < nReads; i++) order[i] = (uint32_t)i;
+		std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lens[a] > lens[b]; });
+		auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+		const size_t oSeq = 0, oRecs = up(seqBytes), oOrder = oRecs + up(nReads * sizeof(gas::SeedRead)), oNext = oOrder + up(nReads * 4);      // (oNext: end of the uploaded part)
+		const size_t oOutN = oNext, oOutSeed = oOutN + up(nReads * 12), total = oOutSeed + up(nReads * p.max_seeds * 12);
+		std::shared_ptr<char> host = owner->hostBlock(oNext);
+		if (!host) return 102;
+		memset(host.get(), 0, oNext);
+		for (size_t i = 0; i < nReads; i++) memcpy(host.get() + recs[i].off, seqs[i], lens[i]);
+		memcpy(host.get() + oRecs, recs.data(), nReads * sizeof(gas::SeedRead));
+		memcpy(host.get() + oOrder, order.data(), nReads * 4);
+		if (total > workBytes)
+		{
+			if (work) hipFree(work);
+			work = nullptr; workBytes = 0;
+			GAS_HIP_OK(hipMalloc(&work, total + total / 8));
+			workBytes = total + total / 8;
+		}
+		// (the kernel waits on dependent loads: directory, keys, entry, coordinate; sixteen waves per CU hide them, and the kernel's
+		// registers and LDS would allow more)
+		const uint32_t slots = (uint32_t)std::min<size_t>(nReads, (size_t)std::max(cus, 1) * kWavesPerCu);
+		const size_t needHits = (size_t)slots * p.max_hits * 20;
+		if (needHits > hitsBytes)
+		{
+			if (hits) hipFree(hits);
+			hits = nullptr; hitsBytes = 0;
+			GAS_HIP_OK(hipMalloc(&hits, needHits));
+			hitsBytes = needHits;
+		}
+		if (!evA) { GAS_HIP_OK(hipEventCreate(&evA)); GAS_HIP_OK(hipEventCreate(&evB)); }
+		uint8_t* w = (uint8_t*)work;
+		GAS_HIP_OK(hipMemcpyAsync(w, host.get(), oNext, hipMemcpyHostToDevice, 0));
+		GAS_HIP_OK(hipMemsetAsync(w + oNext, 0, total - oNext, 0));
+		gas::SeedLaunch L;
+		memset(&L, 0, sizeof(L));
+		L.ix = ix; L.p = p;
+		L.seq = w + oSeq; L.reads = (const gas::SeedRead*)(w + oRecs); L.order = (const uint32_t*)(w + oOrder);
+		L.n_reads = (uint32_t)nReads;
+		const size_t per = (size_t)slots * p.max_hits;
+		L.hit_dx = (int64_t*)hits; L.hit_p = (uint32_t*)((uint8_t*)hits + per * 8); L.hit_node = L.hit_p + per; L.hit_sup = L.hit_node + per;
+		L.out_n = (uint32_t*)(w + oOutN); L.out_seed = (uint32_t*)(w + oOutSeed);
+		GAS_HIP_OK(hipEventRecord(evA, 0));
+		hipLaunchKernelGGL(ga_seed_find_kernel, dim3(slots), dim3(64), 0, 0, L);
+		GAS_HIP_OK(hipEventRecord(evB, 0));
+		std::vector<uint32_t> outN(nReads * 3), outSeed(nReads * p.max_seeds * 3);
+		GAS_HIP_OK(hipMemcpy(outN.data(), w + oOutN, outN.size() * 4, hipMemcpyDeviceToHost));
+		GAS_HIP_OK(hipMemcpy(outSeed.data(), w + oOutSeed, outSeed.size() * 4, hipMemcpyDeviceToHost));
+		GAS_HIP_OK(hipEventSynchronize(evB));
+		float ms = 0;
+		GAS_HIP_OK(hipEventElapsedTime(&ms, evA, evB));
+		out.kernel_ms = ms;
+		for (size_t i = 0; i < nReads; i++) { out.n_seeds[i] = outN[i * 3]; out.n_hits[i] = outN[i * 3 + 1]; out.truncated[i] = outN[i * 3 + 2]; }
+		for (size_t i = 0; i < nReads * p.max_seeds; i++) { out.node[i] = outSeed[i * 3]; out.pos[i] = outSeed[i * 3 + 1]; out.support[i] = outSeed[i * 3 + 2]; }
+		return 0;
+	}
+};
+
+}  // namespace gasd

@@ -96,5 +96,8 @@ struct GaLaunch {
 	uint32_t reserved;
 };
 
+// seeding parameters (include/graphaligner_amd.h: ga_seed_params_t, same fields in the same order)
+struct GaSeedParams { uint32_t k, sample_shift, max_occ, max_hits, window, diag_tol, min_support, max_seeds; };
+
 // row code helpers (host side builds them; GraphAligner.h:2039-2110 for the match sets)
 #define GA_ROW_INVALID 0x80

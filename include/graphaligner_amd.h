@@ -194,6 +194,64 @@ typedef struct ga_batch_stats {
 } ga_batch_stats_t;
 int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out);
 
+/* ---- seeds found on the device ------------------------------------------------------------------------- */
+/* A k-mer index of the uploaded graph and, per batch of reads, up to max_seeds seeds per read in the form ga_align_batch takes.  The rule
+ * (DESIGN.md section 10 has it in full): keys are 2 bits per base (A=0 C=1 G=2 T=3, first base most significant); a k-mer is kept when the
+ * low sample_shift bits of a fixed 64 -> 32 bit mix of its key are zero, the same test for graph and reads; the index holds (key, node
+ * index, offset) of every kept k-mer that lies INSIDE one node (no dummy nodes), ordered by (key, node index, offset).  A read's hits are the
+ * index entries of its kept k-mers whose key has between 1 and max_occ entries, in order of read position p, the first max_hits of them.
+ * Every node has a linear coordinate lin (forward copy: summed length of the bigraph nodes added before it; reverse copy: minus (that sum
+ * + its length - 1)), diag(hit) = lin + offset - p, and support(hit) = hits of the same strand with |p' - p| <= window and |diag' - diag| <=
+ * diag_tol.  Hits with p >= 193, length - p >= 193 and support >= min_support are candidates; they are taken greedily by (support
+ * descending, p, node index, offset), skipping one of the same strand within diag_tol of a taken one.
+ * LIMITS: k-mers that span an edge are not indexed and nodes shorter than k contribute nothing, so a graph of nodes shorter than k has an
+ * empty index; the linear coordinate follows the order in which nodes were added, not topology: it ranks, it never decides an alignment
+ * (a wrongly ranked seed costs a wasted extension); a read shorter than 386 bp gets no seed (either direction would be under the 193 bp the
+ * reference's engine asserts on, GraphAligner.h:906).
+ * Memory kept with the graph (freed by ga_graph_destroy or a new ga_graph_upload): the index (16 bytes per entry, 4 per directory bucket, 8
+ * per node) and, from the first ga_find_seeds on, the last batch's device buffers and the waves' hit buffers (16 waves per CU x max_hits
+ * x 20 bytes: 335 MB at the defaults on 256 CUs).  One ga_find_seeds or index build runs at a time per graph (others wait). */
+typedef struct ga_seed_params {
+	uint32_t k;             /* 11..31 */
+	uint32_t sample_shift;  /* 0..8: one k-mer in 2^sample_shift is kept */
+	uint32_t max_occ;       /* keys with more entries are not used */
+	uint32_t max_hits;      /* per read; 1..65536 */
+	uint32_t window;        /* read positions either side that count as support */
+	uint32_t diag_tol;
+	uint32_t min_support;
+	uint32_t max_seeds;     /* per read; 1..64 */
+} ga_seed_params_t;
+void ga_seed_params_default(ga_seed_params_t* p);   /* k 15, sample_shift 2, max_occ 8, max_hits 4096, window 1024, diag_tol 64, min_support 2, max_seeds 2 */
+
+/* after ga_graph_upload (GA_E_NOT_FINALIZED / GA_E_NO_DEVICE otherwise); replaces an earlier index of this graph; freed with the graph
+ * and dropped by a new ga_graph_upload */
+int ga_graph_build_seed_index(ga_graph_t* g, uint32_t k, uint32_t sample_shift);
+typedef struct ga_seed_index_stats {
+	uint64_t kmers_seen;     /* k-mers inside nodes */
+	uint64_t entries;        /* kept ones = index entries */
+	uint64_t distinct_keys;
+	uint64_t bytes;          /* device memory of the index: 16 per entry + directory + 8 per node */
+	double build_ms;
+	uint32_t k, sample_shift;
+} ga_seed_index_stats_t;
+int ga_graph_seed_index_stats(const ga_graph_t* g, ga_seed_index_stats_t* out);
+/* the index in its order, for tests and tools: the first min(entries, capacity) entries; node INDICES (0 = the dummy start node; bigraph
+ * node number i of a graph built with ga_graph_add_bigraph_node alone is 1 + 2i forward, 2 + 2i reverse) */
+int ga_graph_seed_index_copy(const ga_graph_t* g, uint64_t* keys, uint32_t* node_indices, uint32_t* offsets, size_t capacity);
+
+typedef struct ga_seed_set {
+	size_t n_reads;
+	const size_t* seed_offsets;   /* n_reads + 1: reads[i] owns seeds[seed_offsets[i] .. seed_offsets[i+1]), as ga_align_batch takes them */
+	const ga_seed_t* seeds;
+	const uint32_t* support;      /* per seed */
+	const uint32_t* n_hits;       /* per read: hits used (<= max_hits) */
+	const uint8_t* truncated;     /* per read: 1 when the read had more than max_hits hits */
+	double kernel_ms;             /* HIP-event time of the seeding kernel */
+} ga_seed_set_t;
+/* params == NULL: the defaults.  params->k / sample_shift must be those of the index. */
+int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out);
+void ga_seed_set_free(ga_seed_set_t* s);
+
 /* ---- file formats either side of the path (no libprotobuf; zlib only) --------------------------------- */
 /* gzip-framed vg.Graph chunks (stream.hpp:24-118) -> graph, as DirectedGraph::StreamVGGraphFromFile
  * (BigraphToDigraph.cpp:106-135): all nodes first, then all edges, then Finalize; DBGOverlap stays 0 */

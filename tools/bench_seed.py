@@ -1,0 +1,101 @@
+"""Seeding measured next to the aligner it feeds: the headline workload of bench.py (E. coli-scale linear graph of 64-bp nodes,
+50 000 x 10 kb reads at ONT error) or the bubble graph.  One JSON line on stdout.
+
+Reported: index build time and size; the ga_find_seeds kernel time per batch (HIP events inside the library; warm-up calls, then
+timed calls: median, min, max); reads without a seed; the aligner's kernel_ms for the SAME batch from the reads' true seeds, and the
+ratio of the two, which must stay below 1 (in the overlapped pipeline seeding is a stage in front of the
+kernels).  The aligner from the seeds found here is reported beside it: those seeds lie inside the reads, so every read is two
+extensions where the benchmark's true seeds (first base of the read) make one -- its rate is not comparable with README.md's figures.
+
+    python tools/bench_seed.py --graph linear
+    python tools/bench_seed.py --graph bubbles --reads 50000 --read-len 10000
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--graph", choices=["linear", "bubbles"], default="linear")
+    ap.add_argument("--genome", type=int, default=4641652)
+    ap.add_argument("--node-len", type=int, default=64)
+    ap.add_argument("--reads", type=int, default=50000)
+    ap.add_argument("--read-len", type=int, default=10000)
+    ap.add_argument("--bandwidth", type=int, default=35)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--align-runs", type=int, default=5)
+    args = ap.parse_args()
+
+    import numpy as np
+    # torch before the library: it brings the HIP runtime the library must bind to (tests/conftest.py)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_seed.py needs a GPU: there is no CPU path to time")
+    import __graft_entry__ as entry
+    entry.build_product()
+    from graphaligner_amd import binding, synth
+
+    t0 = time.time()
+    if args.graph == "linear":
+        g = synth.linear_graph(args.genome, node_len=args.node_len, seed=42)
+    else:
+        g = synth.bubble_graph(args.genome, node_len=args.node_len, seed=44)
+    reads, seeds = synth.simulate_reads(g, args.reads, args.read_len, sub=0.04, ins=0.04, dele=0.04, seed=43)
+    gen_s = time.time() - t0
+    G = binding.Graph(gfa=g.gfa())
+    st = G.build_seed_index()
+
+    for _ in range(args.warmup):
+        found = G.find_seeds(reads)
+    ms = []
+    for _ in range(args.calls):
+        found = G.find_seeds(reads)
+        ms.append(found.kernel_ms)
+    ms = np.array(ms)
+
+    def aligner_kernel_ms(rd, sd):
+        rs = binding.ReadSet(rd, sd)
+        b = G.prepare(rs, None, args.bandwidth, 0)
+        out = []
+        for i in range(args.align_runs + 1):
+            b.run()
+            if i:                                       # (the first run warms up)
+                out.append(b.stats()["kernel_ms"])
+        jobs = b.stats()["n_jobs"]
+        res = b.collect(summary=True)
+        b.close()
+        return float(np.median(out)), int(jobs), int(((res["status"] == 0) & (res["failed"] == 0)).sum())
+
+    true_ms, true_jobs, true_ok = aligner_kernel_ms(reads, seeds)
+    have = [i for i in range(len(reads)) if found.seeds[i]]
+    own_ms, own_jobs, own_ok = aligner_kernel_ms([reads[i] for i in have], [found.seeds[i] for i in have])
+    bp = sum(len(r) for r in reads)
+    sup = [s[0] for s in found.support if s]
+    row = {
+        "tool": "tools/bench_seed.py", "graph": args.graph, "genome_bp": args.genome, "node_len": args.node_len, "reads": len(reads), "read_len": args.read_len,
+        "read_bp": bp, "gen_s": round(gen_s, 1),
+        "index": {"k": st["k"], "sample_shift": st["sample_shift"], "kmers_seen": st["kmers_seen"], "entries": st["entries"], "distinct_keys": st["distinct_keys"],
+                  "bytes": st["bytes"], "build_ms": round(st["build_ms"], 2)},
+        "find_seeds_kernel_ms": {"median": round(float(np.median(ms)), 3), "min": round(float(ms.min()), 3), "max": round(float(ms.max()), 3), "calls": len(ms),
+                                 "warmup": args.warmup, "source": "HIP events around the kernel, inside the library"},
+        "find_seeds_Gbp_s": round(bp / float(np.median(ms)) / 1e6, 2),
+        "reads_without_seed": len(reads) - len(have), "truncated_reads": int(sum(found.truncated)),
+        "mean_hits": round(float(np.mean(found.n_hits)), 1), "mean_support_of_first_seed": round(float(np.mean(sup)), 1) if sup else 0.0,
+        "aligner_true_seeds": {"kernel_ms": round(true_ms, 3), "jobs": true_jobs, "reads_aligned": true_ok},
+        "seed_ms_over_aligner_ms": round(float(np.median(ms)) / true_ms, 4),
+        "aligner_own_seeds": {"kernel_ms": round(own_ms, 3), "jobs": own_jobs, "reads_aligned": own_ok,
+                              "note": "seeds inside the reads: two extensions per read (and up to max_seeds seeds), where the true seeds at the first base make one; "
+                                      "not comparable with README.md's rates"},
+    }
+    print(json.dumps(row))
+
+
+if __name__ == "__main__":
+    main()
