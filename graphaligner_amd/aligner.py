@@ -11,7 +11,8 @@ AlignOneWay; here the whole read set is one batch on the GPU (`-t` is accepted a
 list by the reference (:113-117), so with `-t 1` its output order is the reverse of the input order;
 that order is kept.  `-i` (no seeds) and `-A` (augmented graph) are not part of the hot path and
 are refused.  An addition of this project: `--find-seeds` (with `--seed-k K`, `--seed-max N`) stands in
-for `-s`: the seeds come from the library's k-mer index of the graph (binding.Graph.find_seeds).
+for `-s`: the seeds come from the library's k-mer index of the graph (binding.Graph.find_seeds).  `--seed-walks N`
+(1..256; 0, the default: k-mers inside nodes only) builds the walk index, which a graph of nodes shorter than k needs.
 
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq -s seeds.gam -a out.gam -t 1 -b 35
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq --find-seeds -a out.gam -t 1 -b 35
@@ -137,6 +138,7 @@ class AlignerParams:
         self.findSeeds = False
         self.seedK = 15
         self.seedMax = 2
+        self.seedWalks = 0          # --seed-walks: 0 = the in-node index, 1..256 = the walk index with that max_walks
 
 
 def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr, seed_lib_path=None):
@@ -164,8 +166,13 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
     graph = load_graph(params.graphFile, device=device, lib_path=lib_path)
     if find_seeds:
         seeder = graph if seed_lib_path is None else load_graph(params.graphFile, device=device, lib_path=seed_lib_path)
-        st = seeder.build_seed_index(k=params.seedK)
-        out.write("seed index: %d entries of %d k-mers (k %d), %.1f MB\n" % (st["entries"], st["kmers_seen"], st["k"], st["bytes"] / 1e6))
+        walks = getattr(params, "seedWalks", 0)
+        st = seeder.build_seed_index(k=params.seedK, max_walks=walks)
+        line = "seed index: %d entries of %d k-mers (k %d), %.1f MB" % (st["entries"], st["kmers_seen"], st["k"], st["bytes"] / 1e6)
+        if walks:
+            ws = seeder.seed_index_walk_stats()
+            line += ", walks: %d of %d tail starts skipped (more than %d walks)" % (ws["tail_starts_skipped"], ws["tail_starts"], ws["max_walks"])
+        out.write(line + "\n")
         found = seeder.find_seeds([r.sequence for r in reads], max_seeds=params.seedMax)
         seeds_of = {i: s for i, s in enumerate(found.seeds) if s}
         out.write("seeds found for %d of %d reads\n" % (len(seeds_of), len(reads)))
@@ -236,7 +243,7 @@ def parse_args(argv, err=sys.stderr):
     """AlignerMain.cpp:18-107"""
     p = AlignerParams()
     initial_full_band = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max="])
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks="])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -264,6 +271,8 @@ def parse_args(argv, err=sys.stderr):
             p.seedK = int(a)
         elif o == "--seed-max":
             p.seedMax = int(a)
+        elif o == "--seed-walks":
+            p.seedWalks = int(a)
 
     def stop(msg):
         err.write(msg + "\n")
@@ -282,6 +291,8 @@ def parse_args(argv, err=sys.stderr):
         stop("--find-seeds stands in for the seed file: give one of the two")
     if p.findSeeds and not (11 <= p.seedK <= 31 and 1 <= p.seedMax <= 64):
         stop("--seed-k must be 11..31 and --seed-max 1..64")
+    if not 0 <= p.seedWalks <= 256 or (p.seedWalks and not p.findSeeds):
+        stop("--seed-walks must be 0..256 and goes with --find-seeds")
     if initial_full_band:
         stop("-i (alignment without seeds) is not part of the GPU hot path; it asserts in the reference snapshot (GraphAligner.h:1138)")
     if p.auggraphFile != "":

@@ -70,6 +70,11 @@ class GaSeedIndexStats(C.Structure):
                 ("build_ms", C.c_double), ("k", C.c_uint32), ("sample_shift", C.c_uint32)]
 
 
+class GaSeedWalkStats(C.Structure):
+    _fields_ = [("tail_starts", C.c_uint64), ("tail_starts_skipped", C.c_uint64), ("walk_kmers", C.c_uint64), ("duplicates_dropped", C.c_uint64),
+                ("max_walks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class GaSeedSet(C.Structure):
     _fields_ = [("n_reads", C.c_size_t), ("seed_offsets", C.POINTER(C.c_size_t)), ("seeds", C.POINTER(GaSeed)), ("support", C.POINTER(C.c_uint32)),
                 ("n_hits", C.POINTER(C.c_uint32)), ("truncated", C.POINTER(C.c_uint8)), ("kernel_ms", C.c_double)]
@@ -77,7 +82,7 @@ class GaSeedSet(C.Structure):
 
 # the seeding entry points: in the product library and in tests/_build/libga_seed_emul.so, not in the alignment-only emulation
 SEED_EXPORTS = ["ga_seed_params_default", "ga_graph_build_seed_index", "ga_graph_seed_index_stats", "ga_graph_seed_index_copy", "ga_find_seeds",
-                "ga_seed_set_free"]
+                "ga_seed_set_free", "ga_graph_build_seed_index_walks", "ga_graph_seed_index_walk_stats"]
 
 EXPORTS = ["ga_graph_create", "ga_graph_destroy", "ga_graph_add_node", "ga_graph_add_edge", "ga_graph_add_bigraph_node",
            "ga_graph_add_bigraph_edge", "ga_graph_finalize", "ga_graph_load_gfa", "ga_graph_upload", "ga_graph_node_count", "ga_graph_bp",
@@ -131,6 +136,9 @@ def load(path=None):
         L.ga_seed_params_default.restype = None
         L.ga_graph_build_seed_index.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.ga_graph_seed_index_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "ga_graph_build_seed_index_walks"):                  # (bench.py --lib may name a build from before the walk index)
+            L.ga_graph_build_seed_index_walks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+            L.ga_graph_seed_index_walk_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.ga_graph_seed_index_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.ga_find_seeds.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ga_seed_set_free.argtypes = [C.c_void_p]
@@ -196,11 +204,22 @@ class Graph:
         if not hasattr(self.L, "ga_find_seeds"):
             raise RuntimeError("this library has no seeding entry points")
 
-    def build_seed_index(self, k=15, sample_shift=2):
-        """k-mer index of this graph in HBM (replaces an earlier one); returns its statistics"""
+    def build_seed_index(self, k=15, sample_shift=2, max_walks=0):
+        """k-mer index of this graph in HBM (replaces an earlier one); returns its statistics.  max_walks 0: k-mers inside nodes;
+        1..256: the walk index for graphs of short nodes (k-mers across edges, starts with more walks than that left out)"""
         self._need_seeding()
-        _check(self.L, self.L.ga_graph_build_seed_index(self.h, int(k), int(sample_shift)), "ga_graph_build_seed_index")
+        if max_walks:
+            _check(self.L, self.L.ga_graph_build_seed_index_walks(self.h, int(k), int(sample_shift), int(max_walks)), "ga_graph_build_seed_index_walks")
+        else:
+            _check(self.L, self.L.ga_graph_build_seed_index(self.h, int(k), int(sample_shift)), "ga_graph_build_seed_index")
         return self.seed_index_stats()
+
+    def seed_index_walk_stats(self):
+        """tail starts, skipped ones, walk k-mers and dropped duplicates of a walk index (an error for an in-node index)"""
+        self._need_seeding()
+        st = GaSeedWalkStats()
+        _check(self.L, self.L.ga_graph_seed_index_walk_stats(self.h, C.byref(st)), "ga_graph_seed_index_walk_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
 
     def seed_index_stats(self):
         self._need_seeding()

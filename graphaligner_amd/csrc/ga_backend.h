@@ -80,6 +80,8 @@ struct GaEqSource
 
 // ---- seeding (ga_seed.h): a k-mer index of the uploaded graph and, per batch of reads, the seeds it gives ------------------------
 struct GaSeedIndexInfo { uint64_t kmers_seen = 0, entries = 0, distinct_keys = 0, bytes = 0; double build_ms = 0; uint32_t k = 0, sample_shift = 0, dir_bits = 0; };
+// of a walk index (max_walks = 0: the index is an in-node one); walk_kmers: walks of the tail starts that were not skipped
+struct GaSeedWalkInfo { uint32_t max_walks = 0; uint64_t tail_starts = 0, tail_starts_skipped = 0, walk_kmers = 0, duplicates_dropped = 0; };
 // per read r: n_seeds[r] seeds at [r * max_seeds ..): node INDEX, read position and support of each; the number of hits used; truncated
 struct GaSeedOut
 {
@@ -93,6 +95,9 @@ public:
 	virtual ~GaSeedEngine() {}
 	// linx[node] = 2 * lin + strand flag (include/graphaligner_amd.h: the linear coordinate); one per node, dummy nodes included
 	virtual int build(uint32_t k, uint32_t sampleShift, const std::vector<int64_t>& linx) = 0;
+	// the same with the k-mers of walks across edges (maxWalks 1..256); a back end without it refuses (100 = GA_E_INVALID)
+	virtual int buildWalks(uint32_t, uint32_t, uint32_t, const std::vector<int64_t>&) { return 100; }
+	virtual GaSeedWalkInfo walkInfo() const { return GaSeedWalkInfo(); }
 	virtual bool built() const = 0;
 	virtual GaSeedIndexInfo info() const = 0;
 	virtual int copy(uint64_t* keys, uint32_t* nodes, uint32_t* offsets, size_t capacity) const = 0;

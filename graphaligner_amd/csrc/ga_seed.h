@@ -9,7 +9,8 @@
 // the same program because of that discipline.  The one wave primitive that is not a lane block is the exclusive scan of the tile's
 // hit counts (cross-lane DPP/permute moves on the device, a running sum on the host).
 //
-// LIMITS: a k-mer lies inside one node (k-mers across an edge are not indexed; nodes shorter than k contribute nothing).
+// Two indexes: the in-node one (a k-mer lies inside one node; nodes shorter than k contribute nothing) and the walk index, which adds
+// the k-mers of walks that leave a node through its out-edges ("index build with walks" below).  The lookup reads either.
 #pragma once
 #include "ga_types.h"
 #ifndef GA_WAVE_HEADER
@@ -98,6 +99,96 @@ GAS_FN void index_write(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t
 	uint64_t at = firstEntry[node];
 	node_kmers(g, node, k, sampleShift, [&](uint64_t key, uint32_t o) { keys[at] = key; vals[at] = ((uint64_t)node << 32) | o; at++; });
 }
+// ---- index build with walks: k-mers that leave a node through its out-edges -----------------------------------------------------
+// A start (node, o) with o + k > len ("tail start") has one k-mer per walk that begins with the node's bases from o and goes on through
+// out-neighbours until k bases are read; every one is attributed to (node, o).  The walks of one start are enumerated depth first.
+// The stack of the enumeration (per level: next out-edge, end of the out-edges, bases read when the level was entered) is indexed by
+// the depth at run time, so it lives in LDS, lane-minor (level d of lane l at [d][l]: the 64 lanes of a wave hit 64 banks); a level
+// adds at least one base and the last node of a walk is not pushed, so k - 1 <= 30 levels are enough.
+constexpr uint32_t kWalkLevels = 30;
+struct WalkStack { uint32_t cur[kWalkLevels][64], end[kWalkLevels][64], have[kWalkLevels][64]; };
+struct WalkTally { uint64_t tail_starts, skipped, walks; };       // of one lane: tail starts, those over max_walks, walks of the others
+
+// `cnt` <= 31 bases from column `col` on, shifted into `key` (first base most significant)
+GAS_FN uint64_t append_bases(const GaDevGraph& g, uint64_t key, uint64_t col, uint32_t cnt)
+{
+	for (uint32_t i = 0; i < cnt; i++, col++) key = (key << 2) | ((g.seq2[col >> 4] >> ((col & 15) * 2)) & 3u);
+	return key;
+}
+// the walks of the tail start whose own `have` bases are `prefix`: emit(key) per walk in depth-first order; returns their number, or
+// maxWalks + 1 as soon as there are more (what was emitted until then is not to be used: the caller counts first).  A walk does not
+// enter a dummy node or a node of length 0, and one that cannot go on before k bases gives nothing.
+template <class F> GAS_FN uint32_t start_walks(const GaDevGraph& g, uint32_t node, uint64_t prefix, uint32_t have, uint32_t k, uint32_t maxWalks, WalkStack& st, int lane, F emit)
+{
+	uint64_t key = prefix;
+	uint32_t inKey = have, walks = 0;
+	int d = 0;
+	st.cur[0][lane] = g.out_off[node]; st.end[0][lane] = g.out_off[node + 1]; st.have[0][lane] = have;
+	while (d >= 0)
+	{
+		const uint32_t e = st.cur[d][lane];
+		if (e == st.end[d][lane]) { d--; continue; }
+		st.cur[d][lane] = e + 1;
+		const uint32_t m = g.out_nbr[e];
+		if (m == 0 || m + 1 >= g.n_nodes) continue;
+		const uint64_t mStart = g.node_start[m], mLen = g.node_start[m + 1] - mStart;
+		if (mLen == 0) continue;
+		const uint32_t h = st.have[d][lane], need = k - h;
+		key >>= 2 * (inKey - h);                                           // back to the bases read when this level was entered
+		inKey = h;
+		if (mLen >= need)
+		{
+			if (++walks > maxWalks) return walks;
+			emit(append_bases(g, key, mStart, need));
+		}
+		else
+		{
+			key = append_bases(g, key, mStart, (uint32_t)mLen);
+			inKey = h + (uint32_t)mLen;
+			d++;
+			st.cur[d][lane] = g.out_off[m]; st.end[d][lane] = g.out_off[m + 1]; st.have[d][lane] = inKey;
+		}
+	}
+	return walks;
+}
+// the kept k-mers of one node's starts in offset order: the in-node ones as node_kmers gives them, then the tail starts'; returns
+// their number (equal (key, offset) pairs of one start's walks are all emitted: they are dropped after the sort)
+template <class F> GAS_FN uint64_t node_walk_kmers(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t sampleShift, uint32_t maxWalks, WalkStack& st, int lane, WalkTally& tally, F emit)
+{
+	if (node == 0 || node + 1 >= g.n_nodes) return 0;
+	uint64_t n = node_kmers(g, node, k, sampleShift, emit);
+	const uint64_t start = g.node_start[node], len = g.node_start[node + 1] - start;
+	const uint32_t tail = len < k ? (uint32_t)len : k - 1;                  // the last `tail` offsets are tail starts
+	const uint64_t tkey = append_bases(g, 0, start + len - tail, tail);
+	for (uint32_t have = tail; have >= 1; have--)
+	{
+		const uint32_t o = (uint32_t)(len - have);
+		const uint64_t prefix = tkey & ((1ull << (2 * have)) - 1);
+		tally.tail_starts++;
+		const uint32_t walks = start_walks(g, node, prefix, have, k, maxWalks, st, lane, [](uint64_t) {});
+		if (walks > maxWalks) { tally.skipped++; continue; }
+		if (walks == 0) continue;
+		tally.walks += walks;
+		start_walks(g, node, prefix, have, k, maxWalks, st, lane, [&](uint64_t key) { if (kept(key, sampleShift)) { emit(key, o); n++; } });
+	}
+	return n;
+}
+GAS_FN void walk_index_count(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t sampleShift, uint32_t maxWalks, WalkStack& st, int lane, WalkTally& tally, uint64_t* counts)
+{
+	counts[node] = node_walk_kmers(g, node, k, sampleShift, maxWalks, st, lane, tally, [](uint64_t, uint32_t) {});
+}
+GAS_FN void walk_index_write(const GaDevGraph& g, uint32_t node, uint32_t k, uint32_t sampleShift, uint32_t maxWalks, WalkStack& st, int lane, const uint64_t* firstEntry, uint64_t* keys, uint64_t* vals)
+{
+	uint64_t at = firstEntry[node];
+	WalkTally unused{0, 0, 0};
+	node_walk_kmers(g, node, k, sampleShift, maxWalks, st, lane, unused, [&](uint64_t key, uint32_t o) { keys[at] = key; vals[at] = ((uint64_t)node << 32) | o; at++; });
+}
+// after the stable sort equal (key, node, offset) triples are neighbours: entry i stays when it differs from entry i - 1
+GAS_FN uint32_t index_first_of_its_kind(const uint64_t* keys, const uint64_t* vals, uint32_t i)
+{
+	return (i == 0 || keys[i] != keys[i - 1] || vals[i] != vals[i - 1]) ? 1u : 0u;
+}
+
 // entry i (i = n: the end) names itself as the first entry of every bucket between its predecessor's and its own
 GAS_FN void index_dir(const uint64_t* keys, uint32_t n, uint32_t dirShift, uint32_t buckets, uint32_t* dir, uint32_t i)
 {

@@ -41,6 +41,42 @@ __global__ void __launch_bounds__(256) ga_seed_dir_kernel(const uint64_t* keys, 
 	const uint64_t m = __ballot(isNew);
 	if (m != 0 && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(distinct, (unsigned long long)__builtin_popcountll(m));
 }
+// index build with walks: one lane per node as above, one wave per block: the block's LDS is the 64 lanes' walk stacks
+__global__ void __launch_bounds__(64) ga_seed_walk_count_kernel(GaDevGraph g, uint32_t k, uint32_t sampleShift, uint32_t maxWalks, uint64_t* counts, unsigned long long* tally)
+{
+	__shared__ gas::WalkStack st;
+	const uint32_t node = blockIdx.x * 64u + threadIdx.x;
+	gas::WalkTally t{0, 0, 0};
+	if (node < g.n_nodes) gas::walk_index_count(g, node, k, sampleShift, maxWalks, st, (int)threadIdx.x, t, counts);
+	else if (node == g.n_nodes) counts[node] = 0;
+	unsigned long long v[3] = {t.tail_starts, t.skipped, t.walks};
+#pragma unroll
+	for (int q = 0; q < 3; q++)
+	{
+		for (int d = 32; d >= 1; d >>= 1) v[q] += __shfl_down(v[q], d, 64);
+		if (threadIdx.x == 0 && v[q] != 0) atomicAdd(tally + q, v[q]);
+	}
+}
+__global__ void __launch_bounds__(64) ga_seed_walk_write_kernel(GaDevGraph g, uint32_t k, uint32_t sampleShift, uint32_t maxWalks, const uint64_t* firstEntry, uint64_t* keys, uint64_t* vals)
+{
+	__shared__ gas::WalkStack st;
+	const uint32_t node = blockIdx.x * 64u + threadIdx.x;
+	if (node < g.n_nodes) gas::walk_index_write(g, node, k, sampleShift, maxWalks, st, (int)threadIdx.x, firstEntry, keys, vals);
+}
+// equal (key, node, offset) triples are neighbours after the sort: flag the first of each, scan, move the flagged ones
+__global__ void __launch_bounds__(256) ga_seed_flag_kernel(const uint64_t* keys, const uint64_t* vals, uint32_t n, uint32_t* flags)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i < n) flags[i] = gas::index_first_of_its_kind(keys, vals, (uint32_t)i);
+	else if (i == n) flags[i] = 0;                                          // (the scan's last element = the number kept)
+}
+__global__ void __launch_bounds__(256) ga_seed_compact_kernel(const uint64_t* keys, const uint64_t* vals, uint32_t n, const uint32_t* pos, uint64_t* outKeys, uint64_t* outVals)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t at = pos[i];
+	if (pos[i + 1] != at) { outKeys[at] = keys[i]; outVals[at] = vals[i]; }
+}
 // the hot path: one wave per read at a time
 __global__ void __launch_bounds__(64) ga_seed_find_kernel(gas::SeedLaunch L)
 {
@@ -59,6 +95,7 @@ struct DevSeedEngine : GaSeedEngine
 	std::mutex lock;                           // one build or find at a time per graph
 	gas::SeedIndex ix{};
 	GaSeedIndexInfo inf;
+	GaSeedWalkInfo winf;
 	bool have = false;
 	void* dKeys = nullptr; void* dVals = nullptr; void* dDir = nullptr; void* dLinx = nullptr;
 	// buffers of find(), kept between calls
@@ -84,7 +121,16 @@ struct DevSeedEngine : GaSeedEngine
 	bool built() const override { return have; }
 	GaSeedIndexInfo info() const override { return inf; }
 
-	int build(uint32_t k, uint32_t sampleShift, const std::vector<int64_t>& linx) override
+	GaSeedWalkInfo walkInfo() const override { return winf; }
+	int build(uint32_t k, uint32_t sampleShift, const std::vector<int64_t>& linx) override { return buildIndex(k, sampleShift, 0, linx); }
+	int buildWalks(uint32_t k, uint32_t sampleShift, uint32_t maxWalks, const std::vector<int64_t>& linx) override
+	{
+		if (maxWalks < 1 || maxWalks > 256 || k - 1 > gas::kWalkLevels) return 100;
+		return buildIndex(k, sampleShift, maxWalks, linx);
+	}
+
+	// maxWalks = 0: the in-node index
+	int buildIndex(uint32_t k, uint32_t sampleShift, uint32_t maxWalks, const std::vector<int64_t>& linx)
 	{
 		std::lock_guard<std::mutex> guard(lock);
 		GAS_HIP_OK(hipSetDevice(device));
@@ -92,13 +138,23 @@ struct DevSeedEngine : GaSeedEngine
 		const auto t0 = std::chrono::steady_clock::now();
 		const uint32_t nNodes = g.n_nodes;
 		const uint32_t blocks = (nNodes + 1 + 255) / 256;
+		const uint32_t walkBlocks = (nNodes + 1 + 63) / 64;
 		uint64_t* counts = nullptr; uint64_t* firstEntry = nullptr;
 		void* tmp = nullptr; uint64_t* keysIn = nullptr; uint64_t* valsIn = nullptr;
-		auto cleanup = [&]() { for (void* p : {(void*)counts, (void*)firstEntry, tmp, (void*)keysIn, (void*)valsIn}) if (p) hipFree(p); };
+		uint64_t* keysSorted = nullptr; uint64_t* valsSorted = nullptr; uint32_t* flags = nullptr; uint32_t* pos = nullptr; unsigned long long* dTally = nullptr;
+		auto cleanup = [&]() { for (void* p : {(void*)counts, (void*)firstEntry, tmp, (void*)keysIn, (void*)valsIn, (void*)keysSorted, (void*)valsSorted, (void*)flags, (void*)pos, (void*)dTally}) if (p) hipFree(p); };
+		GaSeedWalkInfo w;
+		w.max_walks = maxWalks;
 #define GAS_TRY(call) do { if ((call) != hipSuccess) { fprintf(stderr, "graphaligner_amd: %s failed\n", #call); cleanup(); dropIndex(); return 102; } } while (0)
 		GAS_TRY(hipMalloc((void**)&counts, ((size_t)nNodes + 1) * 8));
 		GAS_TRY(hipMalloc((void**)&firstEntry, ((size_t)nNodes + 1) * 8));
-		hipLaunchKernelGGL(ga_seed_count_kernel, dim3(blocks), dim3(256), 0, 0, g, k, sampleShift, counts);
+		if (maxWalks)
+		{
+			GAS_TRY(hipMalloc((void**)&dTally, 3 * 8));
+			GAS_TRY(hipMemset(dTally, 0, 3 * 8));
+			hipLaunchKernelGGL(ga_seed_walk_count_kernel, dim3(walkBlocks), dim3(64), 0, 0, g, k, sampleShift, maxWalks, counts, dTally);
+		}
+		else hipLaunchKernelGGL(ga_seed_count_kernel, dim3(blocks), dim3(256), 0, 0, g, k, sampleShift, counts);
 		size_t tmpBytes = 0;
 		GAS_TRY(rocprim::exclusive_scan(nullptr, tmpBytes, counts, firstEntry, (uint64_t)0, (size_t)nNodes + 1, rocprim::plus<uint64_t>()));
 		GAS_TRY(hipMalloc(&tmp, std::max<size_t>(tmpBytes, 16)));
@@ -107,20 +163,59 @@ struct DevSeedEngine : GaSeedEngine
 		GAS_TRY(hipMemcpy(&total, firstEntry + nNodes, 8, hipMemcpyDeviceToHost));
 		hipFree(tmp); tmp = nullptr;
 		if (total >= 0xfffffff0ull) { cleanup(); return 100; }             // entry numbers are 32-bit
-		const uint32_t n = (uint32_t)total;
+		uint32_t n = (uint32_t)total;
 		const size_t cap = std::max<size_t>(n, 2);
 		GAS_TRY(hipMalloc((void**)&keysIn, cap * 8));
 		GAS_TRY(hipMalloc((void**)&valsIn, cap * 8));
-		GAS_TRY(hipMalloc(&dKeys, cap * 8));
-		GAS_TRY(hipMalloc(&dVals, cap * 8));
-		hipLaunchKernelGGL(ga_seed_write_kernel, dim3(blocks), dim3(256), 0, 0, g, k, sampleShift, firstEntry, keysIn, valsIn);
+		if (maxWalks)
+		{
+			GAS_TRY(hipMalloc((void**)&keysSorted, cap * 8));
+			GAS_TRY(hipMalloc((void**)&valsSorted, cap * 8));
+			hipLaunchKernelGGL(ga_seed_walk_write_kernel, dim3(walkBlocks), dim3(64), 0, 0, g, k, sampleShift, maxWalks, firstEntry, keysIn, valsIn);
+		}
+		else
+		{
+			GAS_TRY(hipMalloc(&dKeys, cap * 8));
+			GAS_TRY(hipMalloc(&dVals, cap * 8));
+			hipLaunchKernelGGL(ga_seed_write_kernel, dim3(blocks), dim3(256), 0, 0, g, k, sampleShift, firstEntry, keysIn, valsIn);
+		}
 		// by key, stable: equal keys keep the (node, offset) order they were written in
+		uint64_t* sortedK = maxWalks ? keysSorted : (uint64_t*)dKeys;
+		uint64_t* sortedV = maxWalks ? valsSorted : (uint64_t*)dVals;
 		if (n > 0)
 		{
 			tmpBytes = 0;
-			GAS_TRY(rocprim::radix_sort_pairs(nullptr, tmpBytes, keysIn, (uint64_t*)dKeys, valsIn, (uint64_t*)dVals, (size_t)n, 0u, 2u * k));
+			GAS_TRY(rocprim::radix_sort_pairs(nullptr, tmpBytes, keysIn, sortedK, valsIn, sortedV, (size_t)n, 0u, 2u * k));
 			GAS_TRY(hipMalloc(&tmp, std::max<size_t>(tmpBytes, 16)));
-			GAS_TRY(rocprim::radix_sort_pairs(tmp, tmpBytes, keysIn, (uint64_t*)dKeys, valsIn, (uint64_t*)dVals, (size_t)n, 0u, 2u * k));
+			GAS_TRY(rocprim::radix_sort_pairs(tmp, tmpBytes, keysIn, sortedK, valsIn, sortedV, (size_t)n, 0u, 2u * k));
+		}
+		if (maxWalks)
+		{
+			if (tmp) { hipFree(tmp); tmp = nullptr; }
+			// two walks of one start with equal text wrote the same triple twice: one stays
+			unsigned long long tally[3] = {0, 0, 0};
+			GAS_TRY(hipMemcpy(tally, dTally, 3 * 8, hipMemcpyDeviceToHost));
+			w.tail_starts = tally[0]; w.tail_starts_skipped = tally[1]; w.walk_kmers = tally[2];
+			hipFree(keysIn); keysIn = nullptr;
+			hipFree(valsIn); valsIn = nullptr;
+			const uint32_t entryBlocks = (uint32_t)(((uint64_t)n + 1 + 255) / 256);
+			GAS_TRY(hipMalloc((void**)&flags, ((size_t)n + 1) * 4));
+			GAS_TRY(hipMalloc((void**)&pos, ((size_t)n + 1) * 4));
+			hipLaunchKernelGGL(ga_seed_flag_kernel, dim3(entryBlocks), dim3(256), 0, 0, keysSorted, valsSorted, n, flags);
+			tmpBytes = 0;
+			GAS_TRY(rocprim::exclusive_scan(nullptr, tmpBytes, flags, pos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>()));
+			GAS_TRY(hipMalloc(&tmp, std::max<size_t>(tmpBytes, 16)));
+			GAS_TRY(rocprim::exclusive_scan(tmp, tmpBytes, flags, pos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>()));
+			uint32_t unique = 0;
+			GAS_TRY(hipMemcpy(&unique, pos + n, 4, hipMemcpyDeviceToHost));
+			hipFree(tmp); tmp = nullptr;
+			if (unique > n) { cleanup(); return 102; }
+			const size_t ucap = std::max<size_t>(unique, 2);
+			GAS_TRY(hipMalloc(&dKeys, ucap * 8));
+			GAS_TRY(hipMalloc(&dVals, ucap * 8));
+			hipLaunchKernelGGL(ga_seed_compact_kernel, dim3(entryBlocks), dim3(256), 0, 0, keysSorted, valsSorted, n, pos, (uint64_t*)dKeys, (uint64_t*)dVals);
+			w.duplicates_dropped = n - unique;
+			n = unique;
 		}
 		// the directory: top bits of the key -> first entry; about one entry per bucket
 		uint32_t bits = 1;
@@ -144,6 +239,7 @@ struct DevSeedEngine : GaSeedEngine
 		inf.entries = n; inf.distinct_keys = distinct; inf.k = k; inf.sample_shift = sampleShift; inf.dir_bits = bits;
 		inf.bytes = (uint64_t)n * 16 + ((uint64_t)buckets + 1) * 4 + (uint64_t)linx.size() * 8;
 		inf.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		winf = w;
 		have = true;
 		return 0;
 	}

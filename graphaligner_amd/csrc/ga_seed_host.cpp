@@ -46,7 +46,8 @@ void ga_seed_params_default(ga_seed_params_t* p)
 	p->k = 15; p->sample_shift = 2; p->max_occ = 8; p->max_hits = 4096; p->window = 1024; p->diag_tol = 64; p->min_support = 2; p->max_seeds = 2;
 }
 
-int ga_graph_build_seed_index(ga_graph_t* g, uint32_t k, uint32_t sample_shift)
+// max_walks 0: the in-node index
+static int buildIndex(ga_graph_t* g, uint32_t k, uint32_t sample_shift, uint32_t max_walks)
 {
 	GaGraphView v;
 	GaSeedEngine* e = nullptr;
@@ -66,7 +67,28 @@ int ga_graph_build_seed_index(ga_graph_t* g, uint32_t k, uint32_t sample_shift)
 		const int64_t lin = (id & 1) ? -(it->second + len - 1) : it->second;
 		linx[i] = lin * 2 + (id & 1);
 	}
-	return e->build(k, sample_shift, linx);
+	return max_walks ? e->buildWalks(k, sample_shift, max_walks, linx) : e->build(k, sample_shift, linx);
+}
+
+int ga_graph_build_seed_index(ga_graph_t* g, uint32_t k, uint32_t sample_shift) { return buildIndex(g, k, sample_shift, 0); }
+
+int ga_graph_build_seed_index_walks(ga_graph_t* g, uint32_t k, uint32_t sample_shift, uint32_t max_walks)
+{
+	if (max_walks < 1 || max_walks > 256) return GA_E_INVALID;
+	return buildIndex(g, k, sample_shift, max_walks);
+}
+
+int ga_graph_seed_index_walk_stats(const ga_graph_t* g, ga_seed_walk_stats_t* out)
+{
+	GaGraphView v;
+	GaSeedEngine* e = nullptr;
+	if (int s = engineOf(g, v, &e)) return s;
+	if (!out || !e->built()) return GA_E_INVALID;
+	const GaSeedWalkInfo w = e->walkInfo();
+	if (w.max_walks == 0) return GA_E_INVALID;                               // an in-node index
+	out->tail_starts = w.tail_starts; out->tail_starts_skipped = w.tail_starts_skipped; out->walk_kmers = w.walk_kmers;
+	out->duplicates_dropped = w.duplicates_dropped; out->max_walks = w.max_walks; out->reserved = 0;
+	return GA_S_OK;
 }
 
 int ga_graph_seed_index_stats(const ga_graph_t* g, ga_seed_index_stats_t* out)
@@ -79,7 +101,8 @@ int ga_graph_seed_index_stats(const ga_graph_t* g, ga_seed_index_stats_t* out)
 	const std::vector<uint64_t>& start = v.flat->node_start;
 	uint64_t seen = 0;
 	for (size_t i = 1; i + 2 < start.size(); i++) { const uint64_t len = start[i + 1] - start[i]; if (len >= inf.k) seen += len - inf.k + 1; }
-	out->kmers_seen = seen; out->entries = inf.entries; out->distinct_keys = inf.distinct_keys; out->bytes = inf.bytes; out->build_ms = inf.build_ms;
+	out->kmers_seen = seen + e->walkInfo().walk_kmers;                       // (0 for an in-node index)
+	out->entries = inf.entries; out->distinct_keys = inf.distinct_keys; out->bytes = inf.bytes; out->build_ms = inf.build_ms;
 	out->k = inf.k; out->sample_shift = inf.sample_shift;
 	return GA_S_OK;
 }

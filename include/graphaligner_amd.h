@@ -204,8 +204,19 @@ int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out);
  * + its length - 1)), diag(hit) = lin + offset - p, and support(hit) = hits of the same strand with |p' - p| <= window and |diag' - diag| <=
  * diag_tol.  Hits with p >= 193, length - p >= 193 and support >= min_support are candidates; they are taken greedily by (support
  * descending, p, node index, offset), skipping one of the same strand within diag_tol of a taken one.
- * LIMITS: k-mers that span an edge are not indexed and nodes shorter than k contribute nothing, so a graph of nodes shorter than k has an
- * empty index; the linear coordinate follows the order in which nodes were added, not topology: it ranks, it never decides an alignment
+ * Two builds.  ga_graph_build_seed_index: the in-node index above; k-mers that span an edge are not in it and nodes shorter than k
+ * contribute nothing, so a graph of nodes shorter than k has an empty index.  ga_graph_build_seed_index_walks: the WALK index for graphs
+ * of short nodes (variation graphs cut at every variant).  Every base (node, o) of every node but the dummy ones is a start.  o + k <= length:
+ * the one k-mer inside the node, as above.  o + k > length (a "tail start"): one k-mer per walk that begins with the node's bases from o
+ * and goes on through out-neighbours until k bases are read.  A walk never enters a dummy node; one that reaches a node without
+ * out-neighbours before k bases gives nothing; one that enters a node of length 0 gives nothing (so a walk has at most k - 1 edges);
+ * cycles and self-loops are walked like any other edge.  A tail start with more than max_walks walks (walks that give a k-mer; not
+ * distinct keys) contributes nothing at all and is counted: all or nothing, so the index does not depend on the order of a node's
+ * neighbours.  Every kept key gives the entry (key, node index of the START, o), each triple once: walks of one start with equal text
+ * give one entry.  Order, lookup, hits, support, candidates and choice are those above; diag uses the start's node and o.  Both strands
+ * are nodes, so reverse-complement k-mers come from the reverse nodes' own walks.  The index does not depend on where a sequence is cut
+ * into nodes as long as no tail start is skipped; it grows with the variants per k bases (2^v walks over v SNPs).
+ * LIMITS: the linear coordinate follows the order in which nodes were added, not topology: it ranks, it never decides an alignment
  * (a wrongly ranked seed costs a wasted extension); a read shorter than 386 bp gets no seed (either direction would be under the 193 bp the
  * reference's engine asserts on, GraphAligner.h:906).
  * Memory kept with the graph (freed by ga_graph_destroy or a new ga_graph_upload): the index (16 bytes per entry, 4 per directory bucket, 8
@@ -226,8 +237,13 @@ void ga_seed_params_default(ga_seed_params_t* p);   /* k 15, sample_shift 2, max
 /* after ga_graph_upload (GA_E_NOT_FINALIZED / GA_E_NO_DEVICE otherwise); replaces an earlier index of this graph; freed with the graph
  * and dropped by a new ga_graph_upload */
 int ga_graph_build_seed_index(ga_graph_t* g, uint32_t k, uint32_t sample_shift);
+/* the walk index (see above): max_walks 1..256 (GA_E_INVALID otherwise), 64 is a good default.  Entry numbers are 32-bit: a build whose
+ * entries (before equal triples are dropped) would not fit returns GA_E_INVALID; raise sample_shift.  While it is built the device holds
+ * 2 x 16 bytes per such entry + 8 per entry for the removal of equal triples.  Replaces an earlier index of either kind, as
+ * ga_graph_build_seed_index replaces a walk index. */
+int ga_graph_build_seed_index_walks(ga_graph_t* g, uint32_t k, uint32_t sample_shift, uint32_t max_walks);
 typedef struct ga_seed_index_stats {
-	uint64_t kmers_seen;     /* k-mers inside nodes */
+	uint64_t kmers_seen;     /* k-mers inside nodes; walk index: + walk_kmers of ga_seed_walk_stats_t */
 	uint64_t entries;        /* kept ones = index entries */
 	uint64_t distinct_keys;
 	uint64_t bytes;          /* device memory of the index: 16 per entry + directory + 8 per node */
@@ -235,6 +251,15 @@ typedef struct ga_seed_index_stats {
 	uint32_t k, sample_shift;
 } ga_seed_index_stats_t;
 int ga_graph_seed_index_stats(const ga_graph_t* g, ga_seed_index_stats_t* out);
+typedef struct ga_seed_walk_stats {
+	uint64_t tail_starts;          /* starts (node, o) with o + k > length, dummy nodes left out */
+	uint64_t tail_starts_skipped;  /* those with more than max_walks walks: nothing of them is in the index */
+	uint64_t walk_kmers;           /* walks of the tail starts that were not skipped, before sampling */
+	uint64_t duplicates_dropped;   /* kept entries removed because an equal (key, node, offset) was there already */
+	uint32_t max_walks, reserved;
+} ga_seed_walk_stats_t;
+/* GA_E_INVALID when the graph's index is an in-node one (or there is none) */
+int ga_graph_seed_index_walk_stats(const ga_graph_t* g, ga_seed_walk_stats_t* out);
 /* the index in its order, for tests and tools: the first min(entries, capacity) entries; node INDICES (0 = the dummy start node; bigraph
  * node number i of a graph built with ga_graph_add_bigraph_node alone is 1 + 2i forward, 2 + 2i reverse) */
 int ga_graph_seed_index_copy(const ga_graph_t* g, uint64_t* keys, uint32_t* node_indices, uint32_t* offsets, size_t capacity);

@@ -9,6 +9,11 @@ extensions where the benchmark's true seeds (first base of the read) make one --
 
     python tools/bench_seed.py --graph linear
     python tools/bench_seed.py --graph bubbles --reads 50000 --read-len 10000
+    python tools/bench_seed.py --graph bubbles --node-len 8 --max-walks 64
+
+--max-walks N (1..256): the walk index (k-mers across edges; graphs of nodes shorter than k need it, --node-len goes down to 8).  The
+in-node index of the same graph is built and timed first, in the same call ("in_node": its size, build time and ga_find_seeds kernel
+time); everything else in the row is then the walk index's, with its walk statistics.
 """
 import argparse
 import json
@@ -24,7 +29,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graph", choices=["linear", "bubbles"], default="linear")
     ap.add_argument("--genome", type=int, default=4641652)
-    ap.add_argument("--node-len", type=int, default=64)
+    ap.add_argument("--node-len", type=int, default=64, help="8 or more")
+    ap.add_argument("--max-walks", type=int, default=0, help="0: the in-node index; 1..256: the walk index")
     ap.add_argument("--reads", type=int, default=50000)
     ap.add_argument("--read-len", type=int, default=10000)
     ap.add_argument("--bandwidth", type=int, default=35)
@@ -32,6 +38,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--align-runs", type=int, default=5)
     args = ap.parse_args()
+    if args.node_len < 8 or not 0 <= args.max_walks <= 256:
+        raise SystemExit("bench_seed.py: --node-len must be 8 or more and --max-walks 0..256")
 
     import numpy as np
     # torch before the library: it brings the HIP runtime the library must bind to (tests/conftest.py)
@@ -50,15 +58,35 @@ def main():
     reads, seeds = synth.simulate_reads(g, args.reads, args.read_len, sub=0.04, ins=0.04, dele=0.04, seed=43)
     gen_s = time.time() - t0
     G = binding.Graph(gfa=g.gfa())
-    st = G.build_seed_index()
 
-    for _ in range(args.warmup):
-        found = G.find_seeds(reads)
-    ms = []
-    for _ in range(args.calls):
-        found = G.find_seeds(reads)
-        ms.append(found.kernel_ms)
-    ms = np.array(ms)
+    def timed_find():
+        for _ in range(args.warmup):
+            found = G.find_seeds(reads)
+        ms = []
+        for _ in range(args.calls):
+            found = G.find_seeds(reads)
+            ms.append(found.kernel_ms)
+        return found, np.array(ms)
+
+    def index_row(st):
+        return {"k": st["k"], "sample_shift": st["sample_shift"], "kmers_seen": st["kmers_seen"], "entries": st["entries"], "distinct_keys": st["distinct_keys"],
+                "bytes": st["bytes"], "build_ms": round(st["build_ms"], 2)}
+
+    def ms_row(ms):
+        return {"median": round(float(np.median(ms)), 3), "min": round(float(ms.min()), 3), "max": round(float(ms.max()), 3), "calls": len(ms),
+                "warmup": args.warmup, "source": "HIP events around the kernel, inside the library"}
+
+    st = G.build_seed_index()
+    in_node = None
+    if args.max_walks:
+        G.build_seed_index()                                    # (built twice: the first build of a process also loads the kernels)
+        st = G.seed_index_stats()
+        found, ms = timed_find()
+        in_node = {"index": index_row(st), "find_seeds_kernel_ms": ms_row(ms), "reads_without_seed": sum(1 for s in found.seeds if not s)}
+        G.build_seed_index(max_walks=args.max_walks)
+        st = G.build_seed_index(max_walks=args.max_walks)
+        walk = G.seed_index_walk_stats()
+    found, ms = timed_find()
 
     def aligner_kernel_ms(rd, sd):
         rs = binding.ReadSet(rd, sd)
@@ -81,10 +109,8 @@ def main():
     row = {
         "tool": "tools/bench_seed.py", "graph": args.graph, "genome_bp": args.genome, "node_len": args.node_len, "reads": len(reads), "read_len": args.read_len,
         "read_bp": bp, "gen_s": round(gen_s, 1),
-        "index": {"k": st["k"], "sample_shift": st["sample_shift"], "kmers_seen": st["kmers_seen"], "entries": st["entries"], "distinct_keys": st["distinct_keys"],
-                  "bytes": st["bytes"], "build_ms": round(st["build_ms"], 2)},
-        "find_seeds_kernel_ms": {"median": round(float(np.median(ms)), 3), "min": round(float(ms.min()), 3), "max": round(float(ms.max()), 3), "calls": len(ms),
-                                 "warmup": args.warmup, "source": "HIP events around the kernel, inside the library"},
+        "index": index_row(st),
+        "find_seeds_kernel_ms": ms_row(ms),
         "find_seeds_Gbp_s": round(bp / float(np.median(ms)) / 1e6, 2),
         "reads_without_seed": len(reads) - len(have), "truncated_reads": int(sum(found.truncated)),
         "mean_hits": round(float(np.mean(found.n_hits)), 1), "mean_support_of_first_seed": round(float(np.mean(sup)), 1) if sup else 0.0,
@@ -94,6 +120,9 @@ def main():
                               "note": "seeds inside the reads: two extensions per read (and up to max_seeds seeds), where the true seeds at the first base make one; "
                                       "not comparable with README.md's rates"},
     }
+    if args.max_walks:
+        row["walk"] = {key: int(v) for key, v in walk.items()}
+        row["in_node"] = in_node
     print(json.dumps(row))
 
 
