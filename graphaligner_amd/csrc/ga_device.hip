@@ -342,19 +342,22 @@ struct DevGraph : GaBackendGraph
 };
 
 // the few switches the library reads from the environment, once per batch: GA_LANES (1 / 0: force which kernel goes first -- the GPU
-// parity tests run every case both ways), GA_DEBUG_PASSES (one line per launch on stderr) and a test hook for the trace pool's size
+// parity tests run every case both ways), GA_DEBUG_PASSES (one line per launch on stderr) and two test hooks: the trace pool's size
+// and a cap on the waves a launch starts
 struct Knobs
 {
 	int lanes = -1;                 // -1: by graph shape
 	int spread = 1;                 // 1: a small batch is spread over all wave slots; 0: full waves; k > 1: k jobs per wave (GA_LANES_SPREAD, for experiments)
 	bool debugPasses = false;
 	uint64_t tracePoolBytes = 0;    // 0: sized from the batch
+	uint32_t waveSlots = 0;         // 0: as many waves as fit; k: no launch starts more than k (GA_TEST_WAVE_SLOTS: a wave then takes group after group / job after job)
 	Knobs()
 	{
 		if (const char* e = getenv("GA_LANES")) lanes = atoi(e) != 0 ? 1 : 0;
 		debugPasses = getenv("GA_DEBUG_PASSES") != nullptr;
 		if (const char* e = getenv("GA_LANES_SPREAD")) spread = atoi(e);
 		if (const char* t = getenv("GA_TEST_TRACE_POOL_BYTES")) tracePoolBytes = (uint64_t)atoll(t) & ~3ull;
+		if (const char* e = getenv("GA_TEST_WAVE_SLOTS")) waveSlots = (uint32_t)std::max(atoi(e), 0);
 	}
 };
 
@@ -570,7 +573,8 @@ struct DevBatch : GaBackendBatch
 		};
 		gal::WaveLayout lay = layoutFor(LW);
 		const uint64_t fit = scratchBudget() / std::max<uint64_t>(lay.bytes, 1);
-		const uint64_t slotsHere = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g->cus * wavesPerCu, std::max<uint64_t>(fit, 64)));
+		uint64_t slotsHere = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)g->cus * wavesPerCu, std::max<uint64_t>(fit, 64)));
+		if (knobs.waveSlots) slotsHere = std::min<uint64_t>(slotsHere, knobs.waveSlots);
 		// a SMALL batch is spread over all wave slots: a wave's steps cost the same with fewer lanes, and fewer lanes wait for each
 		// other less.  A batch that gives at least six of ten slots a full wave runs in full waves: round 3's kernel is more sensitive
 		// to the waves it shares its CU's memory path with than to the lanes it waits for (50 000 reads: 782 full waves 28.5 ms,
@@ -597,7 +601,7 @@ struct DevBatch : GaBackendBatch
 			float ms = 0;
 			rc = afterPass(ms);
 			if (first) { st.main_ms = ms; st.main_variant = N * 1000 + 80 + (LW == 64 ? 0 : 1); st.slots = waves; st.waves_per_cu = wavesPerCu; st.scratch_bytes = (uint64_t)waves * lay.bytes; }
-			if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: lanes pass <%d,%d>: %zu jobs on %u waves (%.1f GB scratch), %.2f ms\n", N, LW, list.size(), waves, waves * (double)lay.bytes / 1e9, ms);
+			if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: lanes pass <%d,%d>: %zu jobs on %u waves of %u lanes (%.1f GB scratch), %.2f ms\n", N, LW, list.size(), waves, lanesPer, waves * (double)lay.bytes / 1e9, ms);
 #if GA_STAMPS == 3
 			{
 				uint64_t lo = ~0ull, hi = 0, n = 0; double life = 0, cyc = 0, lateStart = 0;
@@ -646,6 +650,7 @@ struct DevBatch : GaBackendBatch
 		Rl.slot_bytes = lay.bytes;
 		const uint64_t fit = scratchBudget() / lay.bytes;
 		uint32_t rslots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((uint64_t)g->cus * wavesPerCuRetry, fit), again.size()));
+		if (knobs.waveSlots) rslots = std::min(rslots, knobs.waveSlots);
 		bool fromPool = false;
 		uint8_t* scratch = takeScratch((size_t)rslots * lay.bytes, fromPool);
 		if (!scratch) return 0;                            // the affected jobs keep their capacity status
@@ -663,7 +668,7 @@ struct DevBatch : GaBackendBatch
 			hipLaunchKernelGGL((ga_extend_kernel<MAXN, GENERAL, SPARSE>), dim3(rslots), dim3(64), 0, stream, Rl);
 			float ms = 0;
 			rc = afterPass(ms);
-			if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d>: %zu jobs on %u slots, %.2f ms\n", MAXN, (int)GENERAL, again.size(), rslots, ms);
+			if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d%s>: %zu jobs on %u slots, %.2f ms\n", MAXN, (int)GENERAL, SPARSE ? ",sparse" : "", again.size(), rslots, ms);
 		}
 		if (fromPool) g->givePool();
 		return rc;

@@ -25,7 +25,8 @@
  * GA_HOST_THREADS (host threads for job building and result assembly; default: the CPUs the process may use), GA_RESULT_POOL_MB,
  * GA_LANES=1/0 (force / forbid the lanes = reads kernel as the first pass; default by the graph's mean node length),
  * GA_LANES_SPREAD=0 / k (full waves / k reads per wave instead of spreading a small batch over all wave slots), GA_DEBUG_PASSES / GA_DEBUG_COLLECT
- * (one line per kernel pass / per host stage on stderr).
+ * (one line per kernel pass / per host stage on stderr), GA_TEST_WAVE_SLOTS=k (a test hook: no kernel pass starts more than k waves, so that
+ * a wave takes one group of reads or one job after the other; unset: as many waves as the device holds).
  */
 #ifndef GRAPHALIGNER_AMD_H
 #define GRAPHALIGNER_AMD_H

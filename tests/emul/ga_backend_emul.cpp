@@ -28,6 +28,59 @@ struct EmulGraph : GaBackendGraph
 	GaDevGraph dev;
 };
 
+// Two switches for what a job finds in its buffers (tests/test_emulated_wave_reuse.py).  On the device a wave's scratch slot and its
+// LDS are never cleared: the first job of a wave finds whatever the allocation held, every later one the leavings of the job before.
+//   GA_EMUL_POISON=1  every buffer a job or a lanes group gets is filled with 0xA5 before its first use (not the sparse method's
+//                     generation-stamped tables: the device zeroes those once per launch, and so does the emulation)
+//   GA_EMUL_REUSE=1   one WaveState and one set of slot buffers per wave-per-read variant, one scratch + LDS image per lanes variant,
+//                     kept across all jobs / groups of a run() and never cleared in between; they grow to the largest job without
+//                     losing what they hold.  The sparse tables are zeroed once per run().  A lanes variant's first (= longest) group
+//                     sets cap_rows / cap_moves for all its groups, as a launch does, so later groups run with larger capacities
+//                     than without the switch: capacities only grow, a job can at most be finished by an earlier pass, and the
+//                     results are expected to be the same (every one is compared with the oracle).
+bool envOn(const char* name) { const char* e = getenv(name); return e && atoi(e); }
+
+template <typename T> void growTo(std::vector<T>& v, size_t n, bool poison)
+{
+	T fill;
+	memset(&fill, poison ? 0xA5 : 0, sizeof(T));
+	if (v.size() < n) v.resize(n, fill);
+}
+
+template <int MAXN> struct SlotBufs
+{
+	std::vector<uint32_t> endA, endB, arena, sliceOff, ckpt, below, ovr;
+	std::vector<uint8_t> flags, staging, sparse;
+	std::unique_ptr<gak::WaveState<MAXN>> ws;
+};
+
+struct LanesBufs
+{
+	std::vector<uint8_t> scratch;
+	std::vector<uint32_t> lds;
+	uint32_t capRows = 0, capMoves = 0;      // GA_EMUL_REUSE: the variant's first (= longest) group sets the layout for all, as a launch does
+};
+
+// GA_EMUL_REUSE: the buffers of every kernel variant, for one run()
+struct KeptBuffers
+{
+	SlotBufs<32> lean32;
+	SlotBufs<64> lean64, general64;
+	SlotBufs<256> general256, sparse256;
+	LanesBufs lanes10, lanes24, lanes56;
+	template <int MAXN, bool GENERAL, bool SPARSE> SlotBufs<MAXN>& slot()
+	{
+		if constexpr (MAXN == 32) { static_assert(!GENERAL && !SPARSE, "no such variant"); return lean32; }
+		else if constexpr (MAXN == 64) { static_assert(!SPARSE, "no such variant"); if constexpr (GENERAL) return general64; else return lean64; }
+		else { static_assert(MAXN == 256 && GENERAL, "no such variant"); if constexpr (SPARSE) return sparse256; else return general256; }
+	}
+	template <int N> LanesBufs& lanes()
+	{
+		static_assert(N == 10 || N == 24 || N == 56, "no such variant");
+		if constexpr (N == 10) return lanes10; else if constexpr (N == 24) return lanes24; else return lanes56;
+	}
+};
+
 struct EmulBatch : GaBackendBatch
 {
 	EmulGraph* g;
@@ -42,24 +95,33 @@ struct EmulBatch : GaBackendBatch
 	uint64_t poolTop = 0;
 	uint64_t retried = 0;
 
+	bool poison = false, reuse = false;
+	std::unique_ptr<KeptBuffers> kept;
+
 	template <int MAXN, bool GENERAL, bool SPARSE = false> void runOne(uint32_t job, uint32_t capCols, uint64_t arenaWords, uint32_t traceCap)
 	{
-		std::vector<uint32_t> endA(capCols), endB(capCols), arena(arenaWords), sliceOff(cfg.max_slices + 1);
-		std::vector<uint8_t> flags(cfg.max_slices + 1);
-		std::vector<uint8_t> staging(traceCap + 64);
-		std::vector<uint32_t> ckpt(cfg.max_slices + 2), below(cfg.max_slices + 1);
+		SlotBufs<MAXN> own;
+		SlotBufs<MAXN>& b = reuse ? kept->slot<MAXN, GENERAL, SPARSE>() : own;
+		growTo(b.endA, capCols, poison); growTo(b.endB, capCols, poison); growTo(b.arena, arenaWords, poison); growTo(b.sliceOff, cfg.max_slices + 1, poison);
+		growTo(b.flags, cfg.max_slices + 1, poison);
+		growTo(b.staging, traceCap + 64, poison);
+		growTo(b.ckpt, cfg.max_slices + 2, poison); growTo(b.below, cfg.max_slices + 1, poison);
 		const uint32_t maxBw = (uint32_t)std::max(std::max(cfg.initial_bw, cfg.ramp_bw), 1);
-		std::vector<uint8_t> sparse(SPARSE ? gak::sparse_mem_bytes(maxBw) : 0);
-		std::vector<uint32_t> ovr(SPARSE ? 2 * (cfg.max_slices + 2) : 0);
-		gak::Slot slot{endA.data(), endB.data(), arena.data(), sliceOff.data(), flags.data(), staging.data(), ckpt.data(), below.data(), SPARSE ? sparse.data() : nullptr, SPARSE ? ovr.data() : nullptr, maxBw};
+		growTo(b.sparse, SPARSE ? gak::sparse_mem_bytes(maxBw) : 0, false);
+		growTo(b.ovr, SPARSE ? 2 * (cfg.max_slices + 2) : 0, poison);
+		gak::Slot slot{b.endA.data(), b.endB.data(), b.arena.data(), b.sliceOff.data(), b.flags.data(), b.staging.data(), b.ckpt.data(), b.below.data(), SPARSE ? b.sparse.data() : nullptr, SPARSE ? b.ovr.data() : nullptr, maxBw};
 		GaLaunch L;
 		memset(&L, 0, sizeof(L));
 		L.graph = g->dev; L.hmm = &g->hmm; L.rows = rows.data(); L.jobs = jobs.data(); L.outs = outs.data();
 		L.traces = pool.data(); L.trace_top = &poolTop; L.trace_pool_cap = pool.size();
 		L.n_jobs = (uint32_t)jobs.size(); L.trace_cap = traceCap; L.cap_cols = capCols; L.max_slices = cfg.max_slices;
 		L.arena_words = arenaWords; L.initial_bw = cfg.initial_bw; L.ramp_bw = cfg.ramp_bw;
-		auto ws = std::make_unique<gak::WaveState<MAXN>>();
-		gak::run_job<MAXN, GENERAL, SPARSE>(L, *ws, slot, job);
+		if (!b.ws)
+		{
+			b.ws = std::make_unique<gak::WaveState<MAXN>>();
+			if (poison) memset(b.ws.get(), 0xA5, sizeof(gak::WaveState<MAXN>));
+		}
+		gak::run_job<MAXN, GENERAL, SPARSE>(L, *b.ws, slot, job);
 	}
 
 	// the lanes = reads program (ga_lanes.h): a wave's 64 lanes are run one after the other through each phase; the points
@@ -75,11 +137,20 @@ struct EmulBatch : GaBackendBatch
 		L.cap_cols = capCols; L.cap_rows = capRows; L.max_slices = cfg.max_slices; L.cap_moves = capMoves;
 		L.initial_bw = cfg.initial_bw; L.ramp_bw = cfg.ramp_bw;
 		L.emit_runs = cfg.emit_runs;
+		LanesBufs own;
+		LanesBufs& b = reuse ? kept->lanes<N>() : own;
+		if (reuse)
+		{
+			if (!b.capRows) { b.capRows = capRows; b.capMoves = capMoves; }
+			capRows = L.cap_rows = std::max(capRows, b.capRows); capMoves = L.cap_moves = std::max(capMoves, b.capMoves);
+		}
 		const WaveLayout lay = wave_layout<N>(capCols, capRows, cfg.max_slices, capMoves);
 		// (on the device the lanes of a wave take their arena blocks from one pool; run one after the other, every lane gets an arena of its own)
 		const uint64_t laneArena = lay.bytes - lay.arena;
-		std::vector<uint8_t> scratch(lay.arena + 64 * laneArena + 256);
-		std::vector<uint32_t> lds((size_t)(Lay<N>::WORDS + kStageWordsLane) * 64);     // tables + the words of the staging image behind them
+		growTo(b.scratch, lay.arena + 64 * laneArena + 256, poison);
+		growTo(b.lds, (size_t)(Lay<N>::WORDS + kStageWordsLane) * 64, poison);         // tables + the words of the staging image behind them
+		std::vector<uint8_t>& scratch = b.scratch;
+		std::vector<uint32_t>& lds = b.lds;
 		std::vector<LaneMem> mem(64);
 		std::vector<LaneState> st(64);
 		for (int lane = 0; lane < 64; lane++)
@@ -123,6 +194,9 @@ struct EmulBatch : GaBackendBatch
 		if (const char* t = getenv("GA_TEST_TRACE_POOL_BYTES")) pool.assign((size_t)atoll(t) & ~(size_t)3, 0);
 		poolTop = 0;
 		retried = 0;
+		poison = envOn("GA_EMUL_POISON");
+		reuse = envOn("GA_EMUL_REUSE");
+		kept = std::make_unique<KeptBuffers>();
 		// first pass: the lanes = reads program, groups of 64 jobs (longest first, as the device queue hands them out), with
 		// deliberately small capacities; what it declines or cannot hold climbs the wave-per-read ladder below
 		const bool lanesFirst = !(getenv("GA_EMUL_NO_LANES") && atoi(getenv("GA_EMUL_NO_LANES")));
@@ -145,6 +219,7 @@ struct EmulBatch : GaBackendBatch
 				}
 				std::vector<uint32_t> again;
 				for (uint32_t j : order) if (outs[j].status == GA_CAP_NODES || outs[j].status == GA_CAP_HEAP || outs[j].status == GA_CAP_COLS || outs[j].status == GA_CAP_ARENA || outs[j].status == GA_CAP_TRACE) again.push_back(j);
+				if (getenv("GA_EMUL_DEBUG")) fprintf(stderr, "emul: lanes pass %d: %zu jobs, %zu move on\n", pass, order.size(), again.size());
 				order.swap(again);
 			}
 		}
@@ -178,6 +253,8 @@ struct EmulBatch : GaBackendBatch
 				runOne<256, true, true>(j, 2000000, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 256 + 6 * 300000), jobs[j].n_rows * 8 + 4096);
 			}
 		}
+		if (getenv("GA_EMUL_DEBUG") && (poison || reuse)) fprintf(stderr, "emul: poison %d, reuse %d\n", (int)poison, (int)reuse);
+		kept.reset();
 		if (getenv("GA_EMUL_DEBUG")) { int hist[100] = {0}; for (auto& o : outs) hist[o.status < 100 ? o.status : 99]++; fprintf(stderr, "emul: %zu jobs, %llu finished by the lanes program, %llu retried; final statuses:", jobs.size(), (unsigned long long)lanesDone, (unsigned long long)retried); for (int i = 0; i < 100; i++) if (hist[i]) fprintf(stderr, " %d:%d", i, hist[i]); fprintf(stderr, "\n"); }
 		return 0;
 	}

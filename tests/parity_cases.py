@@ -1,6 +1,9 @@
 """Parity cases shared by the GPU tests (real library) and the emulated-device tests (the same
 device program executed on the host, tests/emul).  Every case compares the C ABI's results with
 the CPU oracle on identical seeded inputs, bit for bit."""
+import functools
+import re
+
 import numpy as np
 
 from graphaligner_amd import binding, synth
@@ -19,35 +22,42 @@ def case_wave_primitives_on_hardware(lib_path=None):
 RANDOM_GRAPHS = [(64, 0, 0, 0), (64, 100, 1000, 0), (32, 40, 300, 3000), (8, 15, 60, 0), (5, 40, 0, 0)]
 
 
-def case_random_graphs(node_len, snp, indel, sv, lib_path=None):
+def case_random_graphs(node_len, snp, indel, sv, lib_path=None, every_read=False, trace=True):
+    """every_read: no read is let off -- a capacity status is a failure too, and at least 90 % of the reads must have aligned"""
+    n_ok = n_all = 0
     rng = np.random.default_rng(node_len * 1000 + snp)
     g = synth.SynthGraph(synth.random_genome(25000, 500 + node_len), node_len=node_len, snp_every=snp, indel_every=indel, sv_every=sv, seed=node_len)
     for bw, err, length, mid in [(35, 0.04, 2500, False), (35, 0.04, 2500, True), (10, 0.02, 1000, False), (64, 0.1, 1500, True), (2, 0.0, 700, False)]:
         reads, seeds = synth.simulate_reads(g, 12, length, sub=err, ins=err, dele=err, seed=int(rng.integers(1 << 30)), mid_seed=mid)
-        devs, oras = pc.run_both(g.nodes, g.edges, reads, seeds, bw, lib_path=lib_path)
+        devs, oras = pc.run_both(g.nodes, g.edges, reads, seeds, bw, lib_path=lib_path, trace=trace)
         n_cmp = 0
         for i, (d, o) in enumerate(zip(devs, oras)):
-            if d["status"] == 10:
+            if d["status"] == 10 and not every_read:
                 continue      # band wider than the widest kernel variant: reported, not silently wrong
-            pc.compare_read(d, o, "nl%d bw%d read %d" % (node_len, bw, i))
+            pc.compare_read(d, pc.expected(o, trace), "nl%d bw%d read %d" % (node_len, bw, i))
             n_cmp += 1
         assert n_cmp >= len(reads) // 2
+        n_ok += sum(1 for o in oras if o["status"] == 0 and not o["failed"])
+        n_all += len(reads)
+    assert not every_read or n_ok * 10 >= n_all * 9, ("aligned", n_ok, "of", n_all)
 
 
 CYCLIC_GRAPHS = [(4, 10, 6, 1, 2), (8, 35, 8, 2, 5), (16, 35, 5, 3, 3), (32, 80, 9, 0, 8), (12, 35, 12, 2, 1)]
 
 
-def case_cyclic_graphs(node_len, bw, back_edges, self_loops, max_span, lib_path=None):
+def case_cyclic_graphs(node_len, bw, back_edges, self_loops, max_span, lib_path=None, trace=True):
     """bands with strongly connected components (tandem-repeat back edges, self loops): the
     reference relaxes such components with row confirmation (GraphAligner.h:2362-2397); node
     minima, band choice and the trace start depend on the visiting order, so only a faithful
     restatement passes.  Reads are random walks that go round the repeats."""
     g = synth.cyclic_graph(5000, node_len=node_len, seed=node_len + bw, back_edges=back_edges, self_loops=self_loops, max_span=max_span)
-    n_ok = n_cyclic_jobs = 0
+    n_ok = n_cyclic_jobs = n_ora_ok = n_all = 0
     for length, mid in [(400, False), (900, True), (1800, False), (1800, True)]:
         reads, seeds = synth.walk_reads(g, 8, length, seed=length + node_len, mid_seed=mid, first_nodes=max(1, len(g.nodes) // 3))
-        devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, lib_path=lib_path, ctx="cyclic nl%d bw%d len%d" % (node_len, bw, length))
+        devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, lib_path=lib_path, ctx="cyclic nl%d bw%d len%d" % (node_len, bw, length), trace=trace)
         n_ok += sum(1 for d in devs if d["status"] == 0 and not d["failed"])
+        n_ora_ok += sum(1 for o in oras if o["status"] == 0 and not o["failed"])
+        n_all += len(oras)
         # the same batch again through the batch interface: the jobs must have needed the wide (cycle-capable) variant
         gg = binding.Graph(g.nodes, g.edges, lib_path=lib_path)
         b = gg.prepare(reads, seeds, bw)
@@ -55,6 +65,7 @@ def case_cyclic_graphs(node_len, bw, back_edges, self_loops, max_span, lib_path=
         n_cyclic_jobs += b.stats()["jobs_retried"]
     assert n_ok >= 16, n_ok
     assert n_cyclic_jobs > 0
+    return n_ora_ok, n_all          # reads the oracle aligned, reads in all
 
 
 RAMP_CASES = [(8, 5, 35, 0.03), (16, 10, 40, 0.06), (32, 3, 20, 0.03), (64, 15, 80, 0.1)]
@@ -83,20 +94,23 @@ def damaged_reads(reads, rng):
     return out
 
 
-def case_ramp_redo(node_len, bw, ramp, err, lib_path=None):
+def case_ramp_redo(node_len, bw, ramp, err, lib_path=None, trace=True):
     """-B ramp bandwidth: when the HMM turns "wrong" the reference returns to a remembered slice
     and recomputes with the wide band; its checkpoint list is not rewound with it, so the slices
     its traceback recomputes can differ from the ones it kept (and sometimes assert) -- all of
     which has to come out the same."""
     rng = np.random.default_rng(node_len * 7 + bw)
     g = synth.SynthGraph(synth.random_genome(30000, 900 + node_len), node_len=node_len, snp_every=60, indel_every=400, seed=node_len)
-    n_ok = 0
+    n_ok = n_ora_ok = n_all = 0
     for length, mid in [(1500, False), (3000, True), (6000, False)]:
         reads, seeds = synth.simulate_reads(g, 8, length, sub=err, ins=err, dele=err, seed=length + bw, mid_seed=mid)
         reads = damaged_reads(reads, rng)
-        devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib_path, ctx="ramp nl%d bw%d/%d len%d" % (node_len, bw, ramp, length))
+        devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib_path, ctx="ramp nl%d bw%d/%d len%d" % (node_len, bw, ramp, length), trace=trace)
         n_ok += sum(1 for d in devs if d["status"] == 0 and not d["failed"])
+        n_ora_ok += sum(1 for o in oras if o["status"] == 0 and not o["failed"])
+        n_all += len(oras)
     assert n_ok >= 12, n_ok
+    return n_ora_ok, n_all          # reads the oracle aligned, reads in all
 
 
 def case_gfa_overlap(lib_path=None):
@@ -336,7 +350,7 @@ def case_full_size_properties(lib_path=None):
 SPARSE_FANS = [(8, 30000, 150, 600, 35, 0), (8, 30000, 400, 1000, 10, 0), (5, 50000, 100, 333, 35, 60), (12, 20000, 200, 500, 20, 45), (40, 6000, 250, 400, 35, 0)]
 
 
-def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp, lib_path=None):
+def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp, lib_path=None, trace=True):
     """bands of 200 000 cells and more: the reference leaves its bit vectors for calculateSliceAlternate (GraphAligner.h:2148-2329)
     and keeps the window's slices to work the traceback out at once (BacktraceOverride, :167-354).  Fan graphs (synth.FanGraph): a
     stem that ends in many long branches with a common beginning, so that the projected band holds all of them.  Reads through the
@@ -357,7 +371,7 @@ def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp
         pre = synth.add_errors(path[:len(g.head) + len(g.stem) + depth], 0.03, 0.03, 0.03, rng).tobytes().decode()
         post = synth.add_errors(path[len(g.head) + len(g.stem) + depth:], 0.03, 0.03, 0.03, rng).tobytes().decode()
         reads.append(pre + post); seeds.append((3 + b, len(pre), False))
-    devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib_path, ctx="fan %d x %d bw%d/%d" % (branches, branch_len, bw, ramp))
+    devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib_path, ctx="fan %d x %d bw%d/%d" % (branches, branch_len, bw, ramp), trace=trace)
     n_sparse = sum(o["sparse_slices"] for o in oras)
     n_windows = sum(o["override_traces"] for o in oras)
     n_ok = sum(1 for d in devs if d["status"] == 0 and not d["failed"])
@@ -441,3 +455,195 @@ def case_trace_pool_overflow(lib_path=None, monkeypatch=None):
         pc.compare_read(d, o, "small trace pool, read %d" % i)
         n_ok += 1
     assert n_ok >= 8 and n_cap >= 8, (n_ok, n_cap)
+
+
+# ---- full waves, and waves that take several groups or jobs (test_gpu_waves.py, test_emulated_wave_reuse.py) --------------------
+_LANES_LINE = re.compile(r"lanes pass <(\d+),(\d+)>: (\d+) jobs on (\d+) waves of (\d+) lanes")
+_LADDER_LINE = re.compile(r"wave-per-read pass <(\d+),(\d+)(,sparse)?>: (\d+) jobs on (\d+) slots")
+
+
+def debug_passes(err):
+    """the GA_DEBUG_PASSES lines of a run, in order: (variant, jobs, waves, lanes per wave).  variant: "<10,64>" ... for the
+    lanes = reads kernel, "<32,0>" ... "<256,1,sparse>" for the wave-per-read ladder (one job per wave)"""
+    out = []
+    for line in err.splitlines():
+        m = _LANES_LINE.search(line)
+        if m:
+            out.append(("<%s,%s>" % (m.group(1), m.group(2)), int(m.group(3)), int(m.group(4)), int(m.group(5))))
+        m = _LADDER_LINE.search(line)
+        if m:
+            out.append(("<%s,%s%s>" % (m.group(1), m.group(2), m.group(3) or ""), int(m.group(4)), int(m.group(5)), 1))
+    return out
+
+
+def passes_of(passes, variant):
+    """the lines of one variant; a test that cannot find its line fails here"""
+    found = [p for p in passes if p[0] == variant]
+    assert found, ("no debug line for", variant, "among", passes)
+    return found
+
+
+def _mixed_reads(graph, n_long, n_mid, n_short, n_tiny, seed, mid_seed=False):
+    """one batch of reads of 2 500, 1 200 and 400 bp, in shuffled order: lanes of a wave die at different slices and sit out rounds.
+    With mid-read seeds the short reads are 640 bp, so that each half is long enough to align.  `n_tiny` reads are under 256 bp and
+    still align (the lanes kernel declines them, the ladder takes them); one read has an X in it."""
+    reads, seeds = [], []
+    for k, (n, length) in enumerate(((n_long, 2500), (n_mid, 1200), (n_short, 640 if mid_seed else 400), (n_tiny, 400))):
+        r, s = synth.simulate_reads(graph, n, length, seed=seed + k, mid_seed=mid_seed)
+        if k == 3:
+            cut = [200 + 17 * i for i in range(n)]
+            assert all(c < 256 for c in cut)
+            r = [x[:c] for x, c in zip(r, cut)]
+            s = [(a, min(b, c - 1), d) for (a, b, d), c in zip(s, cut)]
+        reads += r
+        seeds += s
+    b = bytearray(reads[n_long].encode()); b[600] = ord("X"); reads[n_long] = b.decode()
+    order = np.random.default_rng(seed).permutation(len(reads))
+    return [reads[i] for i in order], [seeds[i] for i in order]
+
+
+def with_ballast(graph, bp, seed):
+    """`graph` plus a second component of 1 024-bp nodes that no read touches: the library picks its first lanes variant by the
+    graph's mean node length (>= 40 bp: <10,64>, >= 14 bp: <24,32>, else <56,16>), and the ballast moves that mean"""
+    return synth.MultiGraph([graph, synth.SynthGraph(synth.random_genome(bp, seed), node_len=1024, first_id=graph._next_id)])
+
+
+def dense_short_graph():
+    """a plain chain of 64-bp nodes and, as a second component, a stretch with as many bubbles as ten band nodes per lane just hold
+    (a few jobs overflow them); mean node length still >= 40"""
+    chain = synth.linear_graph(400000, node_len=64, seed=31)
+    dense = synth.SynthGraph(synth.random_genome(12000, 32), node_len=64, snp_every=200, indel_every=1000, seed=33, first_id=chain._next_id)
+    return synth.MultiGraph([chain, dense])
+
+
+@functools.lru_cache(maxsize=None)
+def wave_batches(variant, mid_seed=False):
+    """the batches of one lanes variant: [(name, graph, reads, seeds, oracle results)], built once per process and left unchanged.
+    101 / 51 / 25 reads = one full wave of 64 / 32 / 16 lanes and a ragged one (mid-read seeds: 128 reads, two jobs each).
+    The bubbles are as dense as the variant's band nodes allow: a band of some 240 columns holds 10 nodes on 64-bp nodes with a SNP
+    every 1 000 bp (every 100 bp: three jobs of four overflow <10,64>) and 24 nodes on 16-bp nodes with a SNP every 150 bp (every
+    30 bp: nine of ten overflow <24,32>) -- a job that overflows is finished by a later pass, and these batches are about the first."""
+    if variant == "<10,64>":
+        graphs = [("chain64", synth.linear_graph(300000, node_len=64, seed=11)), ("bubbles64", synth.bubble_graph(300000, node_len=64, seed=12, snp_every=1000, indel_every=5000))]
+        mix = (34, 33, 30, 4) if not mid_seed else (44, 43, 41, 0)
+    elif variant == "<24,32>":
+        graphs = [("snps16", with_ballast(synth.SynthGraph(synth.random_genome(100000, 13), node_len=16, snp_every=150, indel_every=1500, seed=14), 150000, 19))]
+        mix = (17, 17, 14, 3)
+    elif variant == "<56,16>":
+        graphs = [("chain8", synth.linear_graph(100000, node_len=8, seed=15)), ("snps8", synth.SynthGraph(synth.random_genome(100000, 16), node_len=8, snp_every=60, seed=17))]
+        mix = (8, 8, 7, 2)
+    else:
+        assert variant == "dense-short"
+        # short reads in a bubble-dense stretch, long ones on a plain chain: jobs are handed out longest first, so a later group
+        # needs more band nodes and more of the arena than the groups its wave carried before
+        g = dense_short_graph()
+        long_r, long_s = synth.simulate_reads(g.parts[0], 40, 2500, seed=41)
+        short_r, short_s = synth.simulate_reads(g.parts[1], 61, 400, seed=42)
+        og = ob.OracleGraph(g.nodes, g.edges)
+        reads, seeds = long_r + short_r, long_s + short_s
+        return [("dense-short", g, reads, seeds, [og.align(r, [s], 35) for r, s in zip(reads, seeds)])]
+    out = []
+    for k, (name, g) in enumerate(graphs):
+        reads, seeds = _mixed_reads(g.parts[0] if isinstance(g, synth.MultiGraph) else g, *mix, seed=100 + 10 * k, mid_seed=mid_seed)
+        og = ob.OracleGraph(g.nodes, g.edges)
+        out.append((name, g, reads, seeds, [og.align(r, [s], 35) for r, s in zip(reads, seeds)]))
+    return out
+
+
+def run_compared(graph, reads, seeds, oras, bw, ramp=0, trace=True, lib_path=None, ctx=""):
+    """one batch through prepare / run / collect: EVERY read is compared with the oracle's result (a capacity status is no oracle
+    status, so it fails here), and at least 90 % of the reads must have aligned.  Returns (results, batch statistics)."""
+    gg = graph if isinstance(graph, binding.Graph) else binding.Graph(graph.nodes, graph.edges, lib_path=lib_path)
+    b = gg.prepare(reads, [s if isinstance(s, list) else [s] for s in seeds], bw, ramp, binding.GA_F_TRACE if trace else 0)
+    b.run()
+    devs = b.collect()
+    assert len(devs) == len(reads) == len(oras)
+    for i, (d, o) in enumerate(zip(devs, oras)):
+        pc.compare_read(d, pc.expected(o, trace), "%s%s read %d" % (ctx, "" if trace else " without trace items", i))
+    n_ok = sum(1 for o in oras if o["status"] == 0 and not o["failed"])
+    assert n_ok * 10 >= len(reads) * 9, (ctx, "aligned", n_ok, "of", len(reads))
+    return devs, b.stats()
+
+
+def same_results(a, b, ctx=""):
+    """two runs of one batch, field by field (also the reads the oracle fails, which compare_read stops at)"""
+    assert len(a) == len(b)
+    for i, (x, y) in enumerate(zip(a, b)):
+        for key in ("status", "failed", "score", "query_position", "alignment_start", "alignment_end", "mappings", "columns"):
+            assert x[key] == y[key], (ctx, "read", i, key, x[key], y[key])
+        assert x["trace"].shape == y["trace"].shape and (x["trace"] == y["trace"]).all(), (ctx, "read", i, "trace items")
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_exits_batch():
+    """(graph, reads, seeds, oracle results), built once per process and left unchanged: one batch on the fan graph of
+    case_sparse_sharp_edges, bandwidth 35 with ramp 70.  The reads are listed longest first, which is the order in which one wave
+    takes their jobs, so an abnormal exit is followed by a normal job and a normal job by an abnormal exit."""
+    g = synth.FanGraph(head_len=200, stem_len=800, n_branches=8, branch_len=30000, shared=300, seed=3)
+    rng = np.random.default_rng(1)
+    on_stem = lambda n: synth.add_errors(np.concatenate([g.stem, g.branches[2]])[:n], 0.03, 0.03, 0.03, rng).tobytes().decode()
+    reads, seeds = [], []
+
+    def add(read, seed):
+        reads.append(read)
+        seeds.append(seed)
+    add(on_stem(1500), (2, 0, False))                  # 0: a seed on the stem, override window at slice 0: the overrideLastJ assertion
+    add(*g.read_through(5, 0, 1400, rng))              # 1: through the fan from the head, aligns
+    add(*g.read_through(1, 0, 1300, rng))              # 2: the same, sparse slices at the ramp width
+    add(reads[0][:1250], (2, 0, False))                # 3: the assertion again, now after a normal job
+    add(*g.read_from_branch(4, 29000, 1100, rng))      # 4: a branch's end and its tail: no fan in sight
+    add(*g.read_through(6, 0, 1000, rng))              # 5: through the fan, shorter
+    add(*g.read_from_branch(0, 20000, 900, rng))       # 6: inside a branch
+    add("", (1, 0, False))                             # 7: degenerate: the empty read asserts
+    add("A", (1, 0, False))                            # 8: degenerate: one base
+    add(*g.read_from_branch(7, 10000, 500, rng))       # 9: a normal job at the end
+    og = ob.OracleGraph(g.nodes, g.edges)
+    return g, reads, seeds, [og.align(r, [s], 35, 70) for r, s in zip(reads, seeds)]
+
+
+def case_mixed_exits_on_one_wave(lib_path=None, trace=True):
+    """abnormal exits between normal jobs (mixed_exits_batch): every read equals the oracle's.  Returns (results, oracle results,
+    batch statistics)"""
+    g, reads, seeds, oras = mixed_exits_batch()
+    gg = binding.Graph(g.nodes, g.edges, lib_path=lib_path)
+    b = gg.prepare(reads, [[s] for s in seeds], 35, 70, binding.GA_F_TRACE if trace else 0)
+    b.run()
+    devs = b.collect()
+    for i, (d, o) in enumerate(zip(devs, oras)):
+        pc.compare_read(d, pc.expected(o, trace), "mixed exits, read %d" % i)
+    assert oras[0]["status"] == 1 and "overrideLastJ" in oras[0]["message"] and oras[3]["status"] == 1 and "overrideLastJ" in oras[3]["message"]
+    assert [o["status"] for o in oras[7:9]] == [1, 0]
+    assert sum(o["sparse_slices"] for o in oras) >= 8
+    assert sum(1 for o in oras if o["status"] == 0 and not o["failed"]) >= 6
+    return devs, oras, b.stats()
+
+
+HOP_MID_LEN, HOP_LAST_LEN = 8, 4
+
+
+@functools.lru_cache(maxsize=None)
+def hop_batch(per_stretch, mid_len=HOP_MID_LEN, last_len=HOP_LAST_LEN):
+    """(nodes, edges, reads, seeds, stretch of each read, oracle results): one chain from plain node and edge lists -- 4 000 nodes
+    of 64 bp (so that the mean node length stays >= 40 and <10,64> goes first), then 3 200 bp in nodes of `mid_len` bp, then 3 200 bp
+    in nodes of `last_len` bp; `per_stretch` reads of 320 bp inside each short-node stretch and 64 on the 64-bp nodes, every seed at
+    its read's first base.  At bandwidth 35 the bands of these reads hold 4-5 nodes of 64 bp; on 8-bp nodes more than the 10 that
+    <10,64> has room for and no more than 24; on 4-bp nodes more than 24 and no more than 56 (on 16- and 8-bp nodes, the first choice,
+    the band of a 320-bp read stayed within 24 nodes on both, so the second hop was never taken)."""
+    lens = [64] * 4000 + [mid_len] * (3200 // mid_len) + [last_len] * (3200 // last_len)
+    mid0, last0 = 4000, 4000 + 3200 // mid_len
+    genome = synth.random_genome(sum(lens), 51)
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    nodes = [(i + 1, genome[starts[i]:starts[i + 1]].tobytes().decode()) for i in range(len(lens))]
+    edges = [(i + 1, False, i + 2, False) for i in range(len(lens) - 1)]
+    assert sum(lens) >= 40 * len(lens)
+    rng = np.random.default_rng(52)
+    reads, seeds, stretch = [], [], []
+    # (first node of a read: far enough from its stretch's end that the read stays inside the stretch)
+    for which, (lo, hi, n) in enumerate(((100, 3900, 64), (mid0 + 40 // mid_len, last0 - 400 // mid_len, per_stretch), (last0 + 40 // last_len, len(lens) - 500 // last_len, per_stretch))):
+        for _ in range(n):
+            node = int(rng.integers(lo, hi))
+            a = int(starts[node])
+            reads.append(synth.add_errors(genome[a:a + 320], 0.03, 0.03, 0.03, rng).tobytes().decode())
+            seeds.append((node + 1, 0, False))
+            stretch.append(which)
+    return nodes, edges, reads, seeds, stretch, pc.oracle_results(nodes, edges, reads, seeds, 35)

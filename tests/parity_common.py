@@ -40,19 +40,36 @@ def compare_read(dev, ora, ctx=""):
     assert dev["columns"] == ora["columns"], (ctx, "column updates", dev["columns"], ora["columns"])
 
 
+# the oracle's results for a batch, computed once per process and left unchanged (the same case runs under several settings of
+# the library: which kernel goes first, how many waves a launch may start, with and without TraceItem lists)
+_ORACLE_MEMO = {}
+
+
+def expected(ora, trace=True):
+    """what compare_read is given for a run with or without TraceItem lists (flags = GA_F_TRACE / 0)"""
+    return ora if trace else dict(ora, trace=np.zeros((0, 7), dtype=np.int64))
+
+
+def oracle_results(nodes, edges, reads, seeds, bw, ramp=0, overlap=0):
+    key = (tuple(map(tuple, nodes)), tuple(map(tuple, edges)), tuple(reads), repr(seeds), bw, ramp, overlap)
+    if key not in _ORACLE_MEMO:
+        og = ob.OracleGraph(nodes, edges, overlap=overlap)
+        oras = []
+        for r, s in zip(reads, seeds):
+            lst = [s] if (len(s) == 3 and not isinstance(s[0], (tuple, list))) else list(s)
+            oras.append(og.align(r, lst, bw, ramp))
+        _ORACLE_MEMO[key] = oras
+    return _ORACLE_MEMO[key]
+
+
 def run_both(nodes, edges, reads, seeds, bw, ramp=0, overlap=0, lib_path=None, trace=True):
-    og = ob.OracleGraph(nodes, edges, overlap=overlap)
     g = binding.Graph(nodes, edges, overlap=overlap, lib_path=lib_path)
     devs = g.align(reads, seeds, bw, ramp, flags=binding.GA_F_TRACE if trace else 0)
-    oras = []
-    for r, s in zip(reads, seeds):
-        lst = [s] if (len(s) == 3 and not isinstance(s[0], (tuple, list))) else list(s)
-        oras.append(og.align(r, lst, bw, ramp))
-    return devs, oras
+    return devs, oracle_results(nodes, edges, reads, seeds, bw, ramp, overlap)
 
 
-def check_parity(nodes, edges, reads, seeds, bw, ramp=0, overlap=0, lib_path=None, ctx=""):
-    devs, oras = run_both(nodes, edges, reads, seeds, bw, ramp, overlap, lib_path)
+def check_parity(nodes, edges, reads, seeds, bw, ramp=0, overlap=0, lib_path=None, ctx="", trace=True):
+    devs, oras = run_both(nodes, edges, reads, seeds, bw, ramp, overlap, lib_path, trace)
     for i, (d, o) in enumerate(zip(devs, oras)):
-        compare_read(d, o, "%s read %d seed %s" % (ctx, i, seeds[i]))
+        compare_read(d, expected(o, trace), "%s read %d seed %s" % (ctx, i, seeds[i]))
     return devs, oras
