@@ -12,7 +12,9 @@ list by the reference (:113-117), so with `-t 1` its output order is the reverse
 that order is kept.  `-i` (no seeds) and `-A` (augmented graph) are not part of the hot path and
 are refused.  An addition of this project: `--find-seeds` (with `--seed-k K`, `--seed-max N`) stands in
 for `-s`: the seeds come from the library's k-mer index of the graph (binding.Graph.find_seeds).  `--seed-walks N`
-(1..256; 0, the default: k-mers inside nodes only) builds the walk index, which a graph of nodes shorter than k needs.
+(1..256; 0, the default: k-mers inside nodes only) builds the walk index, which a graph of nodes shorter than k needs.  `--seed-loci`
+groups a read's hits into loci first and gives one seed per locus (binding.Graph.find_seeds(loci=True)), so that a long read is not
+extended twice from the same place.
 
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq -s seeds.gam -a out.gam -t 1 -b 35
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq --find-seeds -a out.gam -t 1 -b 35
@@ -139,6 +141,7 @@ class AlignerParams:
         self.seedK = 15
         self.seedMax = 2
         self.seedWalks = 0          # --seed-walks: 0 = the in-node index, 1..256 = the walk index with that max_walks
+        self.seedLoci = False       # --seed-loci: one seed per locus
 
 
 def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr, seed_lib_path=None):
@@ -173,9 +176,12 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
             ws = seeder.seed_index_walk_stats()
             line += ", walks: %d of %d tail starts skipped (more than %d walks)" % (ws["tail_starts_skipped"], ws["tail_starts"], ws["max_walks"])
         out.write(line + "\n")
-        found = seeder.find_seeds([r.sequence for r in reads], max_seeds=params.seedMax)
+        by_locus = getattr(params, "seedLoci", False)
+        found = seeder.find_seeds([r.sequence for r in reads], loci=by_locus, max_seeds=params.seedMax)
         seeds_of = {i: s for i, s in enumerate(found.seeds) if s}
         out.write("seeds found for %d of %d reads\n" % (len(seeds_of), len(reads)))
+        if by_locus:
+            out.write("one seed per locus: %d seeds from %d loci\n" % (sum(len(s) for s in found.seeds), sum(found.n_loci)))
 
     # the reference pops reads from the back of the list (Aligner.cpp:113-117)
     order = list(range(len(reads)))[::-1]
@@ -243,7 +249,7 @@ def parse_args(argv, err=sys.stderr):
     """AlignerMain.cpp:18-107"""
     p = AlignerParams()
     initial_full_band = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks="])
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci"])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -273,6 +279,8 @@ def parse_args(argv, err=sys.stderr):
             p.seedMax = int(a)
         elif o == "--seed-walks":
             p.seedWalks = int(a)
+        elif o == "--seed-loci":
+            p.seedLoci = True
 
     def stop(msg):
         err.write(msg + "\n")
@@ -293,6 +301,8 @@ def parse_args(argv, err=sys.stderr):
         stop("--seed-k must be 11..31 and --seed-max 1..64")
     if not 0 <= p.seedWalks <= 256 or (p.seedWalks and not p.findSeeds):
         stop("--seed-walks must be 0..256 and goes with --find-seeds")
+    if p.seedLoci and not p.findSeeds:
+        stop("--seed-loci goes with --find-seeds")
     if initial_full_band:
         stop("-i (alignment without seeds) is not part of the GPU hot path; it asserts in the reference snapshot (GraphAligner.h:1138)")
     if p.auggraphFile != "":

@@ -80,9 +80,16 @@ class GaSeedSet(C.Structure):
                 ("n_hits", C.POINTER(C.c_uint32)), ("truncated", C.POINTER(C.c_uint8)), ("kernel_ms", C.c_double)]
 
 
+class GaSeedSetLoci(C.Structure):
+    """ga_seed_set_t as ga_find_seeds_loci fills it: four more pointers at the end.  Sets of ga_find_seeds are read through GaSeedSet
+    alone, so that a library from before those fields (bench.py --lib) is never read past its own struct."""
+    _fields_ = GaSeedSet._fields_ + [("locus_hits", C.POINTER(C.c_uint32)), ("locus_first_p", C.POINTER(C.c_uint32)),
+                                     ("locus_last_p", C.POINTER(C.c_uint32)), ("n_loci", C.POINTER(C.c_uint32))]
+
+
 # the seeding entry points: in the product library and in tests/_build/libga_seed_emul.so, not in the alignment-only emulation
 SEED_EXPORTS = ["ga_seed_params_default", "ga_graph_build_seed_index", "ga_graph_seed_index_stats", "ga_graph_seed_index_copy", "ga_find_seeds",
-                "ga_seed_set_free", "ga_graph_build_seed_index_walks", "ga_graph_seed_index_walk_stats"]
+                "ga_seed_set_free", "ga_graph_build_seed_index_walks", "ga_graph_seed_index_walk_stats", "ga_find_seeds_loci"]
 
 EXPORTS = ["ga_graph_create", "ga_graph_destroy", "ga_graph_add_node", "ga_graph_add_edge", "ga_graph_add_bigraph_node",
            "ga_graph_add_bigraph_edge", "ga_graph_finalize", "ga_graph_load_gfa", "ga_graph_upload", "ga_graph_node_count", "ga_graph_bp",
@@ -141,6 +148,8 @@ def load(path=None):
             L.ga_graph_seed_index_walk_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.ga_graph_seed_index_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.ga_find_seeds.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        if hasattr(L, "ga_find_seeds_loci"):                               # (nor has such a build seeds per locus)
+            L.ga_find_seeds_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ga_seed_set_free.argtypes = [C.c_void_p]
         L.ga_seed_set_free.restype = None
     _libs[path] = L
@@ -235,10 +244,14 @@ class Graph:
                                                        offs.ctypes.data_as(C.c_void_p), n), "ga_graph_seed_index_copy")
         return keys[:n], nodes[:n], offs[:n]
 
-    def find_seeds(self, reads, **params):
+    def find_seeds(self, reads, loci=False, **params):
         """reads: list of str.  params: fields of ga_seed_params_t that differ from the defaults (k and sample_shift default to the index's).
-        Returns a SeedResult: .seeds = per read a list of (node, pos, reverse), as Graph.prepare / align take them, and the diagnostics."""
+        Returns a SeedResult: .seeds = per read a list of (node, pos, reverse), as Graph.prepare / align take them, and the diagnostics.
+        loci=True: one seed per locus (ga_find_seeds_loci: the read's hits grouped into connected components first); the result then
+        also has .locus_hits, .locus_span and .n_loci."""
         self._need_seeding()
+        if loci and not hasattr(self.L, "ga_find_seeds_loci"):
+            raise RuntimeError("this library has no ga_find_seeds_loci")
         p = GaSeedParams()
         self.L.ga_seed_params_default(C.byref(p))
         st = self.seed_index_stats()
@@ -254,8 +267,11 @@ class Graph:
             arr[i].name = b""
             arr[i].sequence = r
             arr[i].length = len(r)
-        out = C.POINTER(GaSeedSet)()
-        _check(self.L, self.L.ga_find_seeds(self.h, arr, n, C.byref(p), C.byref(out)), "ga_find_seeds")
+        out = C.POINTER(GaSeedSetLoci if loci else GaSeedSet)()
+        if loci:
+            _check(self.L, self.L.ga_find_seeds_loci(self.h, arr, n, C.byref(p), C.byref(out)), "ga_find_seeds_loci")
+        else:
+            _check(self.L, self.L.ga_find_seeds(self.h, arr, n, C.byref(p), C.byref(out)), "ga_find_seeds")
         try:
             S = out.contents
             offs = np.ctypeslib.as_array(S.seed_offsets, shape=(n + 1,)).astype(np.int64) if n else np.zeros(1, dtype=np.int64)
@@ -268,6 +284,12 @@ class Graph:
             res.n_hits = [int(S.n_hits[i]) for i in range(n)]
             res.truncated = [bool(S.truncated[i]) for i in range(n)]
             res.kernel_ms = S.kernel_ms
+            if loci:
+                size = [int(S.locus_hits[i]) for i in range(total)]
+                span = [(int(S.locus_first_p[i]), int(S.locus_last_p[i])) for i in range(total)]
+                res.locus_hits = [size[offs[i]:offs[i + 1]] for i in range(n)]
+                res.locus_span = [span[offs[i]:offs[i + 1]] for i in range(n)]
+                res.n_loci = [int(S.n_loci[i]) for i in range(n)]
             return res
         finally:
             self.L.ga_seed_set_free(out)
@@ -275,8 +297,11 @@ class Graph:
 
 class SeedResult:
     """what Graph.find_seeds returns: seeds[i] = [(node, pos, reverse), ...] of read i (best first, possibly empty), support[i] the
-    seeds' support, n_hits[i] / truncated[i] the read's hit count and whether it was cut at max_hits, kernel_ms the kernel's time"""
+    seeds' support, n_hits[i] / truncated[i] the read's hit count and whether it was cut at max_hits, kernel_ms the kernel's time.
+    With loci=True also locus_hits[i] (per seed: hits of its locus), locus_span[i] (per seed: smallest and largest read position of a
+    hit of its locus) and n_loci[i] (loci of the read that have a candidate); None otherwise"""
     seeds = support = n_hits = truncated = None
+    locus_hits = locus_span = n_loci = None
     kernel_ms = 0.0
 
 

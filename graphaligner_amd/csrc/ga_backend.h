@@ -82,11 +82,14 @@ struct GaEqSource
 struct GaSeedIndexInfo { uint64_t kmers_seen = 0, entries = 0, distinct_keys = 0, bytes = 0; double build_ms = 0; uint32_t k = 0, sample_shift = 0, dir_bits = 0; };
 // of a walk index (max_walks = 0: the index is an in-node one); walk_kmers: walks of the tail starts that were not skipped
 struct GaSeedWalkInfo { uint32_t max_walks = 0; uint64_t tail_starts = 0, tail_starts_skipped = 0, walk_kmers = 0, duplicates_dropped = 0; };
-// per read r: n_seeds[r] seeds at [r * max_seeds ..): node INDEX, read position and support of each; the number of hits used; truncated
+// per read r: n_seeds[r] seeds at [r * max_seeds ..): node INDEX, read position and support of each; the number of hits used; truncated.
+// findLoci also fills, per seed, the hits of its locus and the locus' smallest and largest read position and, per read, the number of
+// loci that have a candidate; find leaves those four empty
 struct GaSeedOut
 {
 	std::vector<uint32_t> n_seeds, n_hits, truncated;
 	std::vector<uint32_t> node, pos, support;
+	std::vector<uint32_t> locus_hits, locus_first_p, locus_last_p, n_loci;
 	double kernel_ms = 0;
 };
 class GaSeedEngine
@@ -103,6 +106,8 @@ public:
 	virtual int copy(uint64_t* keys, uint32_t* nodes, uint32_t* offsets, size_t capacity) const = 0;
 	// reads: seqs[i] of lens[i] characters
 	virtual int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) = 0;
+	// the same with one seed per locus (ga_find_seeds_loci); a back end without it refuses (100 = GA_E_INVALID)
+	virtual int findLoci(const char* const*, const size_t*, size_t, const GaSeedParams&, GaSeedOut&) { return 100; }
 };
 
 class GaBackendGraph

@@ -57,6 +57,13 @@ struct SeedLaunch
 	uint32_t* hit_p; uint32_t* hit_node; int64_t* hit_dx; uint32_t* hit_sup;
 	uint32_t* out_n;                       // [n_reads][3] seeds, hits used, truncated
 	uint32_t* out_seed;                    // [n_reads][max_seeds][3] node index, read position, support
+	// seeds per locus (seed_wave_loci) only; null for seed_wave.  Per wave slot, max_hits entries each: the hit's label (in the end the
+	// smallest hit number of its locus), a second label buffer (in the end the locus' size, at its smallest hit), the locus' largest hit
+	// number (there too), the ends of the hit's window run (first | last << 16) and the locus' best candidate (support << 32 | ~hit
+	// number, there too; 0: none); how many hits the hit is linked to, itself included, 3 for more (<< 16), and for 2 the other one
+	uint32_t* loc_lab; uint32_t* loc_alt; uint32_t* loc_last; uint32_t* loc_run; uint64_t* loc_best; uint32_t* loc_nbr;
+	uint32_t* out_locus;                   // [n_reads][max_seeds][3] hits of the seed's locus, its smallest and its largest read position
+	uint32_t* out_nloci;                   // [n_reads] loci that have a candidate
 };
 
 struct SeedLds
@@ -66,6 +73,7 @@ struct SeedLds
 	uint32_t bestSup[64], bestIdx[64];
 	int64_t taken[64];                                     // 2 * diag + strand of the seeds taken so far
 };
+struct SeedLdsLoci : SeedLds { uint64_t bestKey[64]; };   // seeds per locus: a lane's best locus of the round (its size goes to bestSup)
 
 GAS_FN uint32_t mix64(uint64_t x) { x ^= x >> 29; x *= 0x9e3779b97f4a7c15ull; x ^= x >> 32; return (uint32_t)x; }
 GAS_FN bool kept(uint64_t key, uint32_t sampleShift) { return (mix64(key) & ((1u << sampleShift) - 1u)) == 0; }
@@ -249,8 +257,34 @@ GAS_FN void pack16(const uint8_t* p, uint32_t nValid, uint32_t& code, uint32_t& 
 	}
 }
 
-// one read: its hits into the wave's hit buffer, their support, the greedy choice
-GAS_FN void seed_read(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t read)
+// ---- one read, in three phases: its hits into the wave's hit buffer, their support, the choice ------------------------------------
+// what the first phase leaves for the others: the slot's part of the hit buffer, the number of hits, the read's length
+struct ReadHits { uint32_t* p; uint32_t* node; int64_t* dx; uint32_t* sup; uint32_t n, len; bool truncated; };
+// the slot's part of the buffers of seeds per locus (SeedLaunch)
+struct LociBuf { uint32_t* lab; uint32_t* alt; uint32_t* last; uint32_t* run; uint64_t* best; uint32_t* nbr; };
+
+// Values that several lanes add to or raise in one phase (size, largest hit number and best candidate of a locus, kept at the locus'
+// smallest hit): integer add and max, so the result does not depend on the order.  On gfx950 they are device-scope atomics, which
+// are served by L2; they are set and read back by device-scope stores and loads, which do not stop at the CU's first-level cache (a
+// plain load could find a line there from before the atomics).  On the host they are the plain operations.
+// INVARIANT: between the acc_set of an entry and the end of the read, that entry of `size` (the second label buffer), `last` and `best`
+// is touched by acc_* alone, never by a plain load or store.  The label buffers are used with plain stores and loads again by the
+// next read of the slot; that is sound because every label entry below the read's hit count is written by a plain store (read_support,
+// then every compress and hook step writes the whole buffer) before any plain load reads it, the order the hit buffer itself relies on.
+#ifdef GA_EMULATE
+template <class T> GAS_FN void acc_set(T* p, T v) { *p = v; }
+template <class T> GAS_FN T acc_get(const T* p) { return *p; }
+template <class T> GAS_FN void acc_add(T* p, T v) { *p += v; }
+template <class T> GAS_FN void acc_max(T* p, T v) { if (v > *p) *p = v; }
+#else
+template <class T> GAS_FN void acc_set(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T> GAS_FN T acc_get(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T> GAS_FN void acc_add(T* p, T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T> GAS_FN void acc_max(T* p, T v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#endif
+
+// phase 1: the hits of the read, in (p, index order) order, into the slot's hit buffer (p, node, 2 * diag + strand)
+GAS_FN ReadHits read_hits(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t read)
 {
 	const SeedIndex& ix = L.ix;
 	const GaSeedParams& P = L.p;
@@ -328,11 +362,23 @@ GAS_FN void seed_read(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t
 		}
 	}
 	gaw::wave_sync();                                                        // the hit buffer is complete and visible to every lane
+	return ReadHits{hitP, hitNode, hitDx, hitSup, total, len, truncated};
+}
 
+// phase 2: support of every hit (0 when it is no candidate).  kLoci: also the hit's first label, the smallest hit number among the
+// hits it is linked to (the relation support counts; itself included), the ends of its run, for the later passes over it, and how
+// many hits it is linked to: the relation does not change, so a hit linked to none but itself keeps its label for good, and one linked
+// to a single other hit needs that hit's label and no pass over the run (chance hits are of these two kinds)
+template <bool kLoci> GAS_FN void read_support(const GaSeedParams& P, const ReadHits& h, const LociBuf& b)
+{
+	const uint32_t* hitP = h.p;
+	const int64_t* hitDx = h.dx;
+	uint32_t* hitSup = h.sup;
+	const uint32_t len = h.len;
 	// support: hits are in p order, so the hits within `window` of one are a run around it.  Its two ends come from binary searches;
 	// the count over the run then has no exit that depends on a loaded value, so its loads are in flight together (a walk outwards
 	// that stops at the first hit outside the window waits for every load in turn: 18.1 ms against 13.6 ms for the benchmark's batch)
-	const uint32_t H = total;
+	const uint32_t H = h.n;
 	GAS_LANES(l)
 	{
 		for (uint32_t i = (uint32_t)l; i < H; i += 64)
@@ -344,21 +390,38 @@ GAS_FN void seed_read(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t
 			const uint32_t from = lo;
 			lo = i + 1; hi = H;
 			while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (hitP[mid] - p <= P.window) lo = mid + 1; else hi = mid; }
-			uint32_t sup = 0;
+			uint32_t sup = 0, first = i, last = i;
 #pragma unroll 4
 			for (uint32_t j = from; j < lo; j++)
 			{
 				const int64_t o = hitDx[j];
-				sup += (((o ^ dx) & 1) == 0 && absdiff(o >> 1, dx >> 1) <= (int64_t)P.diag_tol) ? 1u : 0u;       // (j = i counts: the hit itself)
+				const bool linked = ((o ^ dx) & 1) == 0 && absdiff(o >> 1, dx >> 1) <= (int64_t)P.diag_tol;
+				sup += linked ? 1u : 0u;                                         // (j = i counts: the hit itself)
+				if constexpr (kLoci) { first = linked && j < first ? j : first; last = linked ? j : last; }
 			}
 			const bool cand = p >= kMinArm && len - p >= kMinArm && sup >= P.min_support;
 			hitSup[i] = cand ? sup : 0u;
+			if constexpr (kLoci)
+			{
+				b.lab[i] = first; b.run[i] = from | ((lo - 1) << 16);              // (hit numbers are below 65 536 = the largest max_hits)
+				b.nbr[i] = (first < i ? first : last) | ((sup < 3 ? sup : 3u) << 16);
+			}
 		}
 	}
 	gaw::wave_sync();
+}
 
-	// the choice: per round every lane names its best remaining candidate (highest support, then lowest hit number = (p, node, offset)
-	// order), the wave takes the best of those
+// phase 3, hit by hit: per round every lane names its best remaining candidate (highest support, then lowest hit number = (p, node,
+// offset) order), the wave takes the best of those
+GAS_FN void read_choice(const SeedLaunch& L, SeedLds& lds, const ReadHits& h, uint32_t read)
+{
+	const GaSeedParams& P = L.p;
+	const uint32_t* hitP = h.p;
+	const uint32_t* hitNode = h.node;
+	const int64_t* hitDx = h.dx;
+	const uint32_t* hitSup = h.sup;
+	const uint32_t H = h.n;
+	const bool truncated = h.truncated;
 	uint32_t nSeeds = 0;
 	for (uint32_t r = 0; r < P.max_seeds; r++)
 	{
@@ -407,11 +470,223 @@ GAS_FN void seed_read(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t
 	}
 }
 
+// one read: its hits into the wave's hit buffer, their support, the greedy choice
+GAS_FN void seed_read(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t read)
+{
+	const ReadHits h = read_hits(L, lds, slot, read);
+	read_support<false>(L.p, h, LociBuf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+	read_choice(L, lds, h, read);
+}
+
+// ---- seeds per locus -----------------------------------------------------------------------------------------------------------
+// A locus is a connected component of the link relation over the read's hits (include/graphaligner_amd.h has the rule).  Labels: every
+// hit ends up with the smallest hit number of its component.  Two kinds of step, each reading one label buffer and writing the other
+// with a wave_sync between (so a step is a function of the labels before it, on the device as on the host):
+//   hook      label'[i] = the smallest label among the hits linked to i (itself included); the first hook, over label[i] = i, is done by
+//             read_support<true> inside the support scan
+//   compress  label'[i] = the end of the chain label[i], label[label[i]], ... (a label is a hit number of the same component and <= i,
+//             so the labels are pointers towards the component's smallest hit), followed for at most 16 steps; repeated while some
+//             chain was longer (4 passes follow any chain of 65 536 hits; after the first hook a chain has about one step per
+//             `window` of read, so one pass is the rule)
+// until a hook changes nothing: then linked hits have equal labels, so a component has one label, which is one of its hit numbers and
+// <= its smallest.  Labels only fall and every hook carries the smallest number one link further, so H hooks always suffice: both
+// loops have a count as their bound, and their other exit is read by every lane from LDS after a wave_sync.
+GAS_FN bool any_lane(const SeedLds& lds)
+{
+	uint32_t v = 0;
+	for (int l = 0; l < 64; l++) v |= lds.cnt[l];
+	return v != 0;
+}
+
+GAS_FN void seed_read_loci(const SeedLaunch& L, SeedLdsLoci& lds, uint32_t slot, uint32_t read)
+{
+	const GaSeedParams& P = L.p;
+	const ReadHits h = read_hits(L, lds, slot, read);
+	const uint64_t base = (uint64_t)slot * P.max_hits;
+	const LociBuf b{L.loc_lab + base, L.loc_alt + base, L.loc_last + base, L.loc_run + base, L.loc_best + base, L.loc_nbr + base};
+	read_support<true>(P, h, b);
+	const uint32_t H = h.n;
+	uint32_t* a = b.lab;                                                     // the labels as they stand
+	uint32_t* o = b.alt;                                                     // where the next step writes
+	bool changed = true;
+	for (uint32_t round = 0; round < H && changed; round++)
+	{
+		bool moving = true;
+		for (uint32_t c = 0; c < 5 && moving; c++)
+		{
+			GAS_LANES(l)
+			{
+				uint32_t mv = 0;
+				for (uint32_t i = (uint32_t)l; i < H; i += 64)
+				{
+					uint32_t v = a[i], w = a[v];
+					for (uint32_t t = 0; t < 16 && w != v; t++) { v = w; w = a[v]; }
+					o[i] = w;
+					mv |= v ^ w;                                                   // (not at the chain's end yet)
+				}
+				lds.cnt[l] = mv;
+			}
+			gaw::wave_sync();
+			moving = any_lane(lds);
+			gaw::wave_sync();
+			uint32_t* t = a; a = o; o = t;
+		}
+		GAS_LANES(l)
+		{
+			uint32_t ch = 0;
+			for (uint32_t i = (uint32_t)l; i < H; i += 64)
+			{
+				const uint32_t own = a[i], nbr = b.nbr[i], links = nbr >> 16;
+				uint32_t m = own;
+				if (links == 2)
+				{
+					const uint32_t v = a[nbr & 0xffffu];
+					m = v < own ? v : own;
+				}
+				else if (links > 2)
+				{
+					// the smallest label in the run, linked or not: labels are equal all over a locus once it is compressed, so it
+					// is rarely lower than the hit's own, and only then are the diagonals looked at
+					const uint32_t run = b.run[i], from = run & 0xffffu, to = run >> 16;
+					uint32_t low = own;
+#pragma unroll 8
+					for (uint32_t j = from; j <= to; j++) { const uint32_t v = a[j]; low = v < low ? v : low; }
+					if (low < own)
+					{
+						const int64_t dx = h.dx[i];
+#pragma unroll 4
+						for (uint32_t j = from; j <= to; j++)
+						{
+							const uint32_t v = a[j];
+							const int64_t x = h.dx[j];
+							if (v < m && ((x ^ dx) & 1) == 0 && absdiff(x >> 1, dx >> 1) <= (int64_t)P.diag_tol) m = v;
+						}
+					}
+				}
+				o[i] = m;
+				ch |= m ^ own;
+			}
+			lds.cnt[l] = ch;
+		}
+		gaw::wave_sync();
+		changed = any_lane(lds);
+		gaw::wave_sync();
+		uint32_t* t = a; a = o; o = t;
+	}
+
+	// (the sums below rely on changed == false here: `a` is then a compressed buffer that the last hook left as it was, so a[r] == r
+	// names one hit per locus; leaving through round == H cannot happen before that, by the argument above)
+	// per locus, at its smallest hit r (a[r] == r): size, largest hit number (= largest p: hits are in p order) and best candidate
+	// (support << 32 | ~hit number: the larger value is the earlier one in the order of the choice).  A lane sums what its own hits
+	// give to one locus before it adds it there.
+	uint32_t* size = o;
+	GAS_LANES(l)
+	{
+		for (uint32_t i = (uint32_t)l; i < H; i += 64)
+			if (a[i] == i) { acc_set(size + i, 0u); acc_set(b.last + i, 0u); acc_set(b.best + i, (uint64_t)0); }
+	}
+	gaw::wave_sync();
+	GAS_LANES(l)
+	{
+		uint32_t r0 = 0, n = 0, mx = 0;
+		uint64_t bk = 0;
+		for (uint32_t i = (uint32_t)l; i < H; i += 64)
+		{
+			const uint32_t r = a[i];
+			if (n != 0 && r != r0)
+			{
+				acc_add(size + r0, n); acc_max(b.last + r0, mx);
+				if (bk != 0) acc_max(b.best + r0, bk);
+				n = 0; bk = 0;
+			}
+			r0 = r; n++; mx = i;
+			const uint32_t s = h.sup[i];
+			const uint64_t key = ((uint64_t)s << 32) | (0xffffffffu - i);
+			if (s != 0 && key > bk) bk = key;
+		}
+		if (n != 0)
+		{
+			acc_add(size + r0, n); acc_max(b.last + r0, mx);
+			if (bk != 0) acc_max(b.best + r0, bk);
+		}
+	}
+	gaw::wave_sync();
+
+	// the choice, locus by locus: per round every lane names its best remaining locus (most hits, then the earlier seed hit), the wave
+	// takes the best of those; a locus whose seed hit lies within diag_tol of a taken seed hit (itself, once taken) is passed over
+	uint32_t nSeeds = 0, nLoci = 0;
+	for (uint32_t r = 0; r < P.max_seeds; r++)
+	{
+		GAS_LANES(l)
+		{
+			uint32_t bz = 0, roots = 0;
+			uint64_t bk = 0;
+			for (uint32_t i = (uint32_t)l; i < H; i += 64)
+			{
+				if (a[i] != i) continue;
+				const uint64_t key = acc_get(b.best + i);
+				if (key == 0) continue;
+				roots++;
+				const uint32_t z = acc_get(size + i);
+				if (z < bz || (z == bz && key <= bk)) continue;
+				const int64_t dx = h.dx[0xffffffffu - (uint32_t)key];
+				bool same = false;
+				for (uint32_t t = 0; t < r; t++)
+				{
+					const int64_t x = lds.taken[t];
+					if (((x ^ dx) & 1) == 0 && absdiff(x >> 1, dx >> 1) <= (int64_t)P.diag_tol) same = true;
+				}
+				if (!same) { bz = z; bk = key; }
+			}
+			lds.bestSup[l] = bz; lds.bestKey[l] = bk; lds.cnt[l] = roots;
+		}
+		gaw::wave_sync();
+		uint32_t bz = 0;
+		uint64_t bk = 0;
+		for (int l = 0; l < 64; l++)
+		{
+			const uint32_t z = lds.bestSup[l];
+			const uint64_t key = lds.bestKey[l];
+			if (z > bz || (z == bz && key > bk)) { bz = z; bk = key; }
+			if (r == 0) nLoci += lds.cnt[l];
+		}
+		gaw::wave_sync();                                                    // (everyone has read the round's table)
+		if (bz == 0) break;
+		GAS_LANES(l)
+		{
+			if (l == 0)
+			{
+				const uint32_t bi = 0xffffffffu - (uint32_t)bk, root = a[bi];
+				lds.taken[r] = h.dx[bi];
+				uint32_t* s = L.out_seed + ((uint64_t)read * P.max_seeds + r) * 3;
+				s[0] = h.node[bi]; s[1] = h.p[bi]; s[2] = (uint32_t)(bk >> 32);
+				uint32_t* q = L.out_locus + ((uint64_t)read * P.max_seeds + r) * 3;
+				q[0] = bz; q[1] = h.p[root]; q[2] = h.p[acc_get(b.last + root)];
+			}
+		}
+		nSeeds++;
+		gaw::wave_sync();
+	}
+	GAS_LANES(l)
+	{
+		if (l == 0)
+		{
+			uint32_t* q = L.out_n + (uint64_t)read * 3;
+			q[0] = nSeeds; q[1] = H; q[2] = h.truncated ? 1u : 0u;
+			L.out_nloci[read] = nLoci;
+		}
+	}
+}
+
 // a wave: the reads are dealt longest first, round-robin over the waves (read number slot, slot + slots, ... of that order), so every
 // wave gets the same mix of lengths and the hand-out needs no counter: the loop is the same in every lane by construction
 GAS_FN void seed_wave(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t slots)
 {
 	for (uint32_t at = slot; at < L.n_reads; at += slots) seed_read(L, lds, slot, L.order[at]);
+}
+GAS_FN void seed_wave_loci(const SeedLaunch& L, SeedLdsLoci& lds, uint32_t slot, uint32_t slots)
+{
+	for (uint32_t at = slot; at < L.n_reads; at += slots) seed_read_loci(L, lds, slot, L.order[at]);
 }
 
 }  // namespace gas

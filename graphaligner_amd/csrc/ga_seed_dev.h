@@ -83,8 +83,17 @@ __global__ void __launch_bounds__(64) ga_seed_find_kernel(gas::SeedLaunch L)
 	__shared__ gas::SeedLds lds;
 	gas::seed_wave(L, lds, blockIdx.x, gridDim.x);
 }
+// the same with one seed per locus (ga_find_seeds_loci)
+__global__ void __launch_bounds__(64) ga_seed_find_loci_kernel(gas::SeedLaunch L)
+{
+	__shared__ gas::SeedLdsLoci lds;
+	gas::seed_wave_loci(L, lds, blockIdx.x, gridDim.x);
+}
 
 constexpr size_t kWavesPerCu = 16;
+// seeds per locus: its passes over the hits wait on loads more than the lookup does, and 24 waves per CU hide that better (the linear
+// benchmark's batch: 16.2 ms with 16, 13.8 with 20, 12.2 with 24, 16.9 with 28, the most its 67 VGPRs allow: profiles/seed_loci_waves_per_cu.txt)
+constexpr size_t kLociWavesPerCu = 24;
 
 struct DevSeedEngine : GaSeedEngine
 {
@@ -101,6 +110,7 @@ struct DevSeedEngine : GaSeedEngine
 	// buffers of find(), kept between calls
 	void* work = nullptr; size_t workBytes = 0;
 	void* hits = nullptr; size_t hitsBytes = 0;
+	void* loci = nullptr; size_t lociBytes = 0;    // the per-hit buffers of findLoci: allocated at its first call
 	hipEvent_t evA = nullptr, evB = nullptr;
 
 	DevSeedEngine(GaBackendGraph* o, int dev, int nCus, const GaDevGraph& graph) : owner(o), device(dev), cus(nCus), g(graph) {}
@@ -115,6 +125,7 @@ struct DevSeedEngine : GaSeedEngine
 		dropIndex();
 		if (work) hipFree(work);
 		if (hits) hipFree(hits);
+		if (loci) hipFree(loci);
 		if (evA) hipEventDestroy(evA);
 		if (evB) hipEventDestroy(evB);
 	}
@@ -257,12 +268,22 @@ struct DevSeedEngine : GaSeedEngine
 		return 0;
 	}
 
-	int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override
+	int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override { return run(seqs, lens, nReads, p, out, false); }
+	int findLoci(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override { return run(seqs, lens, nReads, p, out, true); }
+
+	// byLocus: one seed per locus (ga_seed_find_loci_kernel) instead of hit by hit
+	int run(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out, bool byLocus)
 	{
 		std::lock_guard<std::mutex> guard(lock);
 		if (!have) return 100;
 		out.n_seeds.assign(nReads, 0); out.n_hits.assign(nReads, 0); out.truncated.assign(nReads, 0);
 		out.node.assign(nReads * p.max_seeds, 0); out.pos.assign(nReads * p.max_seeds, 0); out.support.assign(nReads * p.max_seeds, 0);
+		out.locus_hits.clear(); out.locus_first_p.clear(); out.locus_last_p.clear(); out.n_loci.clear();
+		if (byLocus)
+		{
+			out.locus_hits.assign(nReads * p.max_seeds, 0); out.locus_first_p.assign(nReads * p.max_seeds, 0); out.locus_last_p.assign(nReads * p.max_seeds, 0);
+			out.n_loci.assign(nReads, 0);
+		}
 		out.kernel_ms = 0;
 		if (nReads == 0) return 0;
 		GAS_HIP_OK(hipSetDevice(device));
@@ -280,7 +301,8 @@ struct DevSeedEngine : GaSeedEngine
 		std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lens[a] > lens[b]; });
 		auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
 		const size_t oSeq = 0, oRecs = up(seqBytes), oOrder = oRecs + up(nReads * sizeof(gas::SeedRead)), oNext = oOrder + up(nReads * 4);      // (oNext: end of the uploaded part)
-		const size_t oOutN = oNext, oOutSeed = oOutN + up(nReads * 12), total = oOutSeed + up(nReads * p.max_seeds * 12);
+		const size_t oOutN = oNext, oOutSeed = oOutN + up(nReads * 12), oOutLocus = oOutSeed + up(nReads * p.max_seeds * 12);
+		const size_t oOutNLoci = oOutLocus + (byLocus ? up(nReads * p.max_seeds * 12) : 0), total = oOutNLoci + (byLocus ? up(nReads * 4) : 0);
 		std::shared_ptr<char> host = owner->hostBlock(oNext);
 		if (!host) return 102;
 		memset(host.get(), 0, oNext);
@@ -296,7 +318,7 @@ struct DevSeedEngine : GaSeedEngine
 		}
 		// (the kernel waits on dependent loads: directory, keys, entry, coordinate; sixteen waves per CU hide them, and the kernel's
 		// registers and LDS would allow more)
-		const uint32_t slots = (uint32_t)std::min<size_t>(nReads, (size_t)std::max(cus, 1) * kWavesPerCu);
+		const uint32_t slots = (uint32_t)std::min<size_t>(nReads, (size_t)std::max(cus, 1) * (byLocus ? kLociWavesPerCu : kWavesPerCu));
 		const size_t needHits = (size_t)slots * p.max_hits * 20;
 		if (needHits > hitsBytes)
 		{
@@ -304,6 +326,14 @@ struct DevSeedEngine : GaSeedEngine
 			hits = nullptr; hitsBytes = 0;
 			GAS_HIP_OK(hipMalloc(&hits, needHits));
 			hitsBytes = needHits;
+		}
+		const size_t needLoci = byLocus ? (size_t)slots * p.max_hits * 28 : 0;
+		if (needLoci > lociBytes)
+		{
+			if (loci) hipFree(loci);
+			loci = nullptr; lociBytes = 0;
+			GAS_HIP_OK(hipMalloc(&loci, needLoci));
+			lociBytes = needLoci;
 		}
 		if (!evA) { GAS_HIP_OK(hipEventCreate(&evA)); GAS_HIP_OK(hipEventCreate(&evB)); }
 		uint8_t* w = (uint8_t*)work;
@@ -317,8 +347,14 @@ struct DevSeedEngine : GaSeedEngine
 		const size_t per = (size_t)slots * p.max_hits;
 		L.hit_dx = (int64_t*)hits; L.hit_p = (uint32_t*)((uint8_t*)hits + per * 8); L.hit_node = L.hit_p + per; L.hit_sup = L.hit_node + per;
 		L.out_n = (uint32_t*)(w + oOutN); L.out_seed = (uint32_t*)(w + oOutSeed);
+		if (byLocus)
+		{
+			L.loc_best = (uint64_t*)loci; L.loc_lab = (uint32_t*)((uint8_t*)loci + per * 8); L.loc_alt = L.loc_lab + per; L.loc_last = L.loc_alt + per; L.loc_run = L.loc_last + per; L.loc_nbr = L.loc_run + per;
+			L.out_locus = (uint32_t*)(w + oOutLocus); L.out_nloci = (uint32_t*)(w + oOutNLoci);
+		}
 		GAS_HIP_OK(hipEventRecord(evA, 0));
-		hipLaunchKernelGGL(ga_seed_find_kernel, dim3(slots), dim3(64), 0, 0, L);
+		if (byLocus) hipLaunchKernelGGL(ga_seed_find_loci_kernel, dim3(slots), dim3(64), 0, 0, L);
+		else hipLaunchKernelGGL(ga_seed_find_kernel, dim3(slots), dim3(64), 0, 0, L);
 		GAS_HIP_OK(hipEventRecord(evB, 0));
 		std::vector<uint32_t> outN(nReads * 3), outSeed(nReads * p.max_seeds * 3);
 		GAS_HIP_OK(hipMemcpy(outN.data(), w + oOutN, outN.size() * 4, hipMemcpyDeviceToHost));
@@ -329,6 +365,13 @@ struct DevSeedEngine : GaSeedEngine
 		out.kernel_ms = ms;
 		for (size_t i = 0; i < nReads; i++) { out.n_seeds[i] = outN[i * 3]; out.n_hits[i] = outN[i * 3 + 1]; out.truncated[i] = outN[i * 3 + 2]; }
 		for (size_t i = 0; i < nReads * p.max_seeds; i++) { out.node[i] = outSeed[i * 3]; out.pos[i] = outSeed[i * 3 + 1]; out.support[i] = outSeed[i * 3 + 2]; }
+		if (byLocus)
+		{
+			std::vector<uint32_t> outLocus(nReads * p.max_seeds * 3);
+			GAS_HIP_OK(hipMemcpy(outLocus.data(), w + oOutLocus, outLocus.size() * 4, hipMemcpyDeviceToHost));
+			GAS_HIP_OK(hipMemcpy(out.n_loci.data(), w + oOutNLoci, nReads * 4, hipMemcpyDeviceToHost));
+			for (size_t i = 0; i < nReads * p.max_seeds; i++) { out.locus_hits[i] = outLocus[i * 3]; out.locus_first_p[i] = outLocus[i * 3 + 1]; out.locus_last_p[i] = outLocus[i * 3 + 2]; }
+		}
 		return 0;
 	}
 };

@@ -18,6 +18,7 @@ struct SeedSetOwner
 	std::vector<ga_seed_t> seeds;
 	std::vector<uint32_t> support, nHits;
 	std::vector<uint8_t> truncated;
+	std::vector<uint32_t> locusHits, locusFirstP, locusLastP, nLoci;        // ga_find_seeds_loci only
 };
 
 bool paramsOk(const ga_seed_params_t& p)
@@ -116,7 +117,8 @@ int ga_graph_seed_index_copy(const ga_graph_t* g, uint64_t* keys, uint32_t* node
 	return e->copy(keys, node_indices, offsets, capacity);
 }
 
-int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out)
+// byLocus: ga_find_seeds_loci
+static int findSeeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out, bool byLocus)
 {
 	GaGraphView v;
 	GaSeedEngine* e = nullptr;
@@ -131,8 +133,9 @@ int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, c
 	for (size_t i = 0; i < n_reads; i++) { seqs[i] = reads[i].sequence; lens[i] = reads[i].length; if (lens[i] && !seqs[i]) return GA_E_INVALID; }
 	const GaSeedParams bp{p.k, p.sample_shift, p.max_occ, p.max_hits, p.window, p.diag_tol, p.min_support, p.max_seeds};
 	GaSeedOut r;
-	if (int s = e->find(seqs.data(), lens.data(), n_reads, bp, r)) return s;
+	if (int s = byLocus ? e->findLoci(seqs.data(), lens.data(), n_reads, bp, r) : e->find(seqs.data(), lens.data(), n_reads, bp, r)) return s;
 	SeedSetOwner* o = new SeedSetOwner();
+	memset(&o->pub, 0, sizeof(o->pub));
 	o->offsets.assign(n_reads + 1, 0);
 	o->nHits.assign(r.n_hits.begin(), r.n_hits.end());
 	o->truncated.assign(n_reads, 0);
@@ -148,6 +151,7 @@ int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, c
 			sd.node_id = id >> 1; sd.read_pos = r.pos[at]; sd.reverse = (int32_t)(id & 1);
 			o->seeds.push_back(sd);
 			o->support.push_back(r.support[at]);
+			if (byLocus) { o->locusHits.push_back(r.locus_hits[at]); o->locusFirstP.push_back(r.locus_first_p[at]); o->locusLastP.push_back(r.locus_last_p[at]); }
 		}
 		o->offsets[i + 1] = o->seeds.size();
 	}
@@ -155,8 +159,24 @@ int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, c
 	o->seeds.reserve(1); o->support.reserve(1); o->nHits.reserve(1); o->truncated.reserve(1);
 	o->pub.n_reads = n_reads; o->pub.seed_offsets = o->offsets.data(); o->pub.seeds = o->seeds.data(); o->pub.support = o->support.data();
 	o->pub.n_hits = o->nHits.data(); o->pub.truncated = o->truncated.data(); o->pub.kernel_ms = r.kernel_ms;
+	if (byLocus)
+	{
+		o->nLoci.assign(r.n_loci.begin(), r.n_loci.end());
+		o->locusHits.reserve(1); o->locusFirstP.reserve(1); o->locusLastP.reserve(1); o->nLoci.reserve(1);
+		o->pub.locus_hits = o->locusHits.data(); o->pub.locus_first_p = o->locusFirstP.data(); o->pub.locus_last_p = o->locusLastP.data(); o->pub.n_loci = o->nLoci.data();
+	}
 	*out = &o->pub;
 	return GA_S_OK;
+}
+
+int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out)
+{
+	return findSeeds(g, reads, n_reads, params, out, false);
+}
+
+int ga_find_seeds_loci(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out)
+{
+	return findSeeds(g, reads, n_reads, params, out, true);
 }
 
 void ga_seed_set_free(ga_seed_set_t* s)

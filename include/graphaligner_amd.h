@@ -220,9 +220,25 @@ int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out);
  * LIMITS: the linear coordinate follows the order in which nodes were added, not topology: it ranks, it never decides an alignment
  * (a wrongly ranked seed costs a wasted extension); a read shorter than 386 bp gets no seed (either direction would be under the 193 bp the
  * reference's engine asserts on, GraphAligner.h:906).
+ * ONE SEED PER LOCUS (ga_find_seeds_loci).  Along a long read the diagonal drifts (the read's indels, the file-order coordinate stepping
+ * at every bubble), so the second hit ga_find_seeds takes is usually the first one's place again, further along.  ga_find_seeds_loci
+ * groups the hits first.  Hits, their order, strand, diag, support, candidates and the truncation at max_hits are those above.  LINK: two
+ * different hits i and j are linked when they have the same strand, |p_i - p_j| <= window and |diag_i - diag_j| <= diag_tol (the relation
+ * support counts).  LOCUS: a connected component of the link relation over all hits the read keeps after truncation, candidates or not;
+ * locus_hits is its size, locus_first_p and locus_last_p the smallest and largest p in it.  SEED HIT of a locus: its first candidate in the
+ * order above (support descending, p, node index, offset); a locus without a candidate gives nothing, and n_loci of a read counts the
+ * loci that have one.  CHOICE: the loci that have a candidate, ordered by locus_hits descending, then by their seed hits in the order
+ * above, are taken greedily up to max_seeds; a locus is skipped when its seed hit has the same strand as an already taken seed hit and
+ * lies within diag_tol of it (the skip of ga_find_seeds, kept: it covers one diagonal broken by a gap wider than window).  One seed per
+ * taken locus is returned, in that order.  Loci are ranked by size because the best-supported single hit can lie in a partial copy of a
+ * repeat: with max_seeds = 1 ga_find_seeds_loci can therefore name a different seed than ga_find_seeds does.  A structural variant longer
+ * than diag_tol still splits a locus in two (the coordinate is file order), which costs one extension.
  * Memory kept with the graph (freed by ga_graph_destroy or a new ga_graph_upload): the index (16 bytes per entry, 4 per directory bucket, 8
  * per node) and, from the first ga_find_seeds on, the last batch's device buffers and the waves' hit buffers (16 waves per CU x max_hits
- * x 20 bytes: 335 MB at the defaults on 256 CUs).  One ga_find_seeds or index build runs at a time per graph (others wait). */
+ * x 20 bytes: 335 MB at the defaults on 256 CUs).  ga_find_seeds_loci runs 24 waves per CU and keeps 28 bytes more per hit (labels, locus
+ * sizes, ends, best candidates and link counts): from its first call on the buffers are 24 waves per CU x max_hits x 48 bytes, 1.2 GB at
+ * those figures; a caller of ga_find_seeds alone never pays that.  One
+ * ga_find_seeds, ga_find_seeds_loci or index build runs at a time per graph (others wait). */
 typedef struct ga_seed_params {
 	uint32_t k;             /* 11..31 */
 	uint32_t sample_shift;  /* 0..8: one k-mer in 2^sample_shift is kept */
@@ -273,9 +289,16 @@ typedef struct ga_seed_set {
 	const uint32_t* n_hits;       /* per read: hits used (<= max_hits) */
 	const uint8_t* truncated;     /* per read: 1 when the read had more than max_hits hits */
 	double kernel_ms;             /* HIP-event time of the seeding kernel */
+	/* ga_find_seeds_loci only (all four NULL in a set returned by ga_find_seeds) */
+	const uint32_t* locus_hits;     /* per seed: hits of its locus */
+	const uint32_t* locus_first_p;  /* per seed: smallest read position of a hit of its locus */
+	const uint32_t* locus_last_p;   /* per seed: largest one */
+	const uint32_t* n_loci;         /* per read: loci that have a candidate (>= its seeds) */
 } ga_seed_set_t;
 /* params == NULL: the defaults.  params->k / sample_shift must be those of the index. */
 int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out);
+/* one seed per locus (see above): the same contract, and the set is freed the same way */
+int ga_find_seeds_loci(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out);
 void ga_seed_set_free(ga_seed_set_t* s);
 
 /* ---- file formats either side of the path (no libprotobuf; zlib only) --------------------------------- */

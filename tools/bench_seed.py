@@ -14,6 +14,11 @@ extensions where the benchmark's true seeds (first base of the read) make one --
 --max-walks N (1..256): the walk index (k-mers across edges; graphs of nodes shorter than k need it, --node-len goes down to 8).  The
 in-node index of the same graph is built and timed first, in the same call ("in_node": its size, build time and ga_find_seeds kernel
 time); everything else in the row is then the walk index's, with its walk statistics.
+
+--loci: one seed per locus (ga_find_seeds_loci) measured beside ga_find_seeds on the same batch and index, the timed calls of the two
+alternating: "loci" holds the grouped kernel's time, its seeds, the jobs and the aligner's kernel_ms from them, its ratio to the
+aligner's kernel_ms from true seeds, and the two sums seeding kernel + aligner kernels, grouped and ungrouped, with the saving and the
+min-max spreads it has to exceed.
 """
 import argparse
 import json
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--align-runs", type=int, default=5)
+    ap.add_argument("--loci", action="store_true", help="also measure ga_find_seeds_loci (one seed per locus)")
     args = ap.parse_args()
     if args.node_len < 8 or not 0 <= args.max_walks <= 256:
         raise SystemExit("bench_seed.py: --node-len must be 8 or more and --max-walks 0..256")
@@ -59,13 +65,22 @@ def main():
     gen_s = time.time() - t0
     G = binding.Graph(gfa=g.gfa())
 
+    grouped = {}
+
     def timed_find():
+        """with --loci the grouped call runs after every ungrouped one, warm-up included (its result and times go to `grouped`)"""
         for _ in range(args.warmup):
             found = G.find_seeds(reads)
-        ms = []
+            if args.loci:
+                G.find_seeds(reads, loci=True)
+        ms, ms_loci = [], []
         for _ in range(args.calls):
             found = G.find_seeds(reads)
             ms.append(found.kernel_ms)
+            if args.loci:
+                grouped["found"] = G.find_seeds(reads, loci=True)
+                ms_loci.append(grouped["found"].kernel_ms)
+        grouped["ms"] = np.array(ms_loci)
         return found, np.array(ms)
 
     def index_row(st):
@@ -99,7 +114,10 @@ def main():
         jobs = b.stats()["n_jobs"]
         res = b.collect(summary=True)
         b.close()
+        spreads.append(max(out) - min(out))
         return float(np.median(out)), int(jobs), int(((res["status"] == 0) & (res["failed"] == 0)).sum())
+
+    spreads = []                                        # max - min of every aligner measurement, in call order
 
     true_ms, true_jobs, true_ok = aligner_kernel_ms(reads, seeds)
     have = [i for i in range(len(reads)) if found.seeds[i]]
@@ -120,6 +138,27 @@ def main():
                               "note": "seeds inside the reads: two extensions per read (and up to max_seeds seeds), where the true seeds at the first base make one; "
                                       "not comparable with README.md's rates"},
     }
+    if args.loci:
+        lf, lms = grouped["found"], grouped["ms"]
+        lhave = [i for i in range(len(reads)) if lf.seeds[i]]
+        loci_ms, loci_jobs, loci_ok = aligner_kernel_ms([reads[i] for i in lhave], [lf.seeds[i] for i in lhave])
+        size = [s[0] for s in lf.locus_hits if s]
+        sum_own, sum_loci = float(np.median(ms)) + own_ms, float(np.median(lms)) + loci_ms
+        row["loci"] = {
+            "find_seeds_loci_kernel_ms": ms_row(lms),
+            "loci_kernel_over_find_seeds_kernel": round(float(np.median(lms)) / float(np.median(ms)), 3),
+            "seeds": sum(len(s) for s in lf.seeds), "seeds_ungrouped": sum(len(s) for s in found.seeds),
+            "reads_with_two_seeds": sum(1 for s in lf.seeds if len(s) > 1), "reads_with_two_seeds_ungrouped": sum(1 for s in found.seeds if len(s) > 1),
+            "reads_without_seed": len(reads) - len(lhave), "loci_with_candidate": int(sum(lf.n_loci)),
+            "first_seed_equals_ungrouped_first_seed": sum(1 for a, b in zip(lf.seeds, found.seeds) if a[:1] == b[:1]),
+            "mean_hits_of_first_locus": round(float(np.mean(size)), 1) if size else 0.0,
+            "aligner_grouped_seeds": {"kernel_ms": round(loci_ms, 3), "jobs": loci_jobs, "reads_aligned": loci_ok},
+            "seed_ms_over_aligner_ms": round(float(np.median(lms)) / true_ms, 4),
+            "seeding_plus_aligner_ms": {"ungrouped": round(sum_own, 3), "grouped": round(sum_loci, 3), "saving": round(sum_own - sum_loci, 3),
+                                        "spread_ungrouped": round(float(ms.max() - ms.min()) + spreads[1], 3),
+                                        "spread_grouped": round(float(lms.max() - lms.min()) + spreads[2], 3),
+                                        "note": "medians; a spread is max - min of the seeding calls plus max - min of the aligner runs"},
+        }
     if args.max_walks:
         row["walk"] = {key: int(v) for key, v in walk.items()}
         row["in_node"] = in_node
