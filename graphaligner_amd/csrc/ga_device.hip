@@ -25,9 +25,9 @@ namespace {
 
 struct SlotLayout
 {
-	uint64_t endPrev, endCur, sliceOff, arena, trace, flags, ckpt, belowOff, sparse, ovr, bytes;
+	uint64_t endPrev, endCur, sliceOff, arena, trace, flags, ckpt, belowOff, sparse, ovr, state, bytes;
 };
-__host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxSlices, uint64_t arenaWords, uint32_t traceCap, uint32_t sparseBw = 0)
+__host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxSlices, uint64_t arenaWords, uint32_t traceCap, uint32_t sparseBw = 0, uint64_t stateBytes = 0)
 {
 	auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
 	SlotLayout l;
@@ -43,6 +43,8 @@ __host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxS
 	// the variant that carries the sparse method: its tables (first, so that the host can clear them) and the override windows
 	l.sparse = at; if (sparseBw) at = up(at + gak::sparse_mem_bytes(sparseBw));
 	l.ovr = at; if (sparseBw) at = up(at + 8ull * (maxSlices + 2));
+	// the variant whose band tables do not fit in LDS: its WaveState (0 bytes for every other variant)
+	l.state = at; if (stateBytes) at = up(at + stateBytes);
 	l.bytes = at;
 	return l;
 }
@@ -74,6 +76,39 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GA_WAVE
 		if (k >= L.n_jobs) break;                      // every wave reaches this exit once the queue is drained
 		uint32_t job = L.job_list ? L.job_list[k] : k;
 		gak::run_job<MAXN, GENERAL, SPARSE>(L, ws, slot, job);
+		__syncthreads();
+	}
+}
+
+// ---- bands of up to 4 096 nodes: the same program with its band tables (WaveState<4096>, some 780 KB) in the wave's scratch slot in
+// HBM instead of LDS.  The last bit-vector pass of the ladder, for the few jobs whose band overflowed 256 nodes or whose projection
+// heap overflowed: one wave per CU at most.  The state is not cleared between jobs, as LDS is not; lanes hand values to each other
+// through it, which ws_order / ws_handover (ga_kernel.h) order with a workgroup-scope fence in this kernel.
+constexpr int kWideNodes = 4096;
+constexpr uint32_t kCutoffCols = gak::kCutoff;       // (a band of this many columns is no bit-vector band)
+__global__ void __launch_bounds__(64) ga_wide_kernel(GaLaunch L)
+{
+	const SlotLayout lay = slotLayout(L.cap_cols, L.max_slices, L.arena_words, L.trace_cap, 0u, sizeof(gak::WaveState<kWideNodes>));
+	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.slot_bytes;
+	gak::WaveState<kWideNodes>& ws = *(gak::WaveState<kWideNodes>*)(base + lay.state);
+	gak::Slot slot;
+	slot.end_prev = (uint32_t*)(base + lay.endPrev);
+	slot.end_cur = (uint32_t*)(base + lay.endCur);
+	slot.slice_off = (uint32_t*)(base + lay.sliceOff);
+	slot.arena = (uint32_t*)(base + lay.arena);
+	slot.trace = base + lay.trace;
+	slot.slice_flags = base + lay.flags;
+	slot.ckpt = (uint32_t*)(base + lay.ckpt);
+	slot.below_off = (uint32_t*)(base + lay.belowOff);
+	slot.sparse = nullptr;
+	slot.ovr = nullptr;
+	slot.sparse_max_bw = 0u;
+	while (true)
+	{
+		uint32_t k = gaw::wave_atomic_add(L.next_job, 1u);
+		if (k >= L.n_jobs) break;                      // every wave reaches this exit once the queue is drained
+		uint32_t job = L.job_list ? L.job_list[k] : k;
+		gak::run_job<kWideNodes, true, false>(L, ws, slot, job);
 		__syncthreads();
 	}
 }
@@ -540,6 +575,8 @@ struct DevBatch : GaBackendBatch
 	static bool needsGeneral(int s) { return s == GA_UNSUPPORTED_CYCLE || s == GA_UNSUPPORTED_RAMP; }
 	// what a lanes = reads variant with larger tables can still take
 	static bool widerLanes(int s) { return s == GA_CAP_NODES || s == GA_CAP_COLS || s == GA_CAP_ARENA || s == GA_CAP_TRACE || s == GA_CAP_HEAP; }
+	// what the pass with 4 096 band nodes is for: the band tables or the projection heap of 256 nodes overflowed
+	static bool widerTables(int s) { return s == GA_CAP_NODES || s == GA_CAP_HEAP; }
 
 	// one launch of the lanes = reads kernel over `list` (job indices, longest first)
 	template <int N, int LW> int lanesPass(const std::vector<uint32_t>& list, uint32_t rowsPerSlice, bool first)
@@ -627,12 +664,18 @@ struct DevBatch : GaBackendBatch
 		return rc;
 	}
 
+	// (MAXN > 256: the variant with its band tables in HBM, ga_wide_kernel; it takes only the jobs whose band or projection heap overflowed)
 	template <int MAXN, bool GENERAL, bool SPARSE = false> int retryPass(uint32_t capCols, uint64_t arenaWordsPerSlice, uint32_t traceMul, uint32_t wavesPerCuRetry, bool takeCapacity, bool takeGeneral,
 	                                                                    uint64_t arenaWordsExtra = 0)
 	{
+		constexpr bool kWide = gak::Limits<MAXN>::kStateInHbm;
+		static_assert(!kWide || (MAXN == kWideNodes && GENERAL && !SPARSE), "one variant keeps its state in HBM");
 		std::vector<uint32_t> again;
 		for (uint32_t i : orderHost)
-			if ((takeCapacity && isCapacity(outs[i].status)) || (takeGeneral && needsGeneral(outs[i].status)) || (SPARSE && outs[i].status == GA_UNSUPPORTED_BAND)) again.push_back(i);
+		{
+			if (kWide) { if (widerTables(outs[i].status)) again.push_back(i); }
+			else if ((takeCapacity && isCapacity(outs[i].status)) || (takeGeneral && needsGeneral(outs[i].status)) || (SPARSE && outs[i].status == GA_UNSUPPORTED_BAND)) again.push_back(i);
+		}
 		if (again.empty()) return 0;
 		if (ensureRows()) return GA_E_DEVICE;
 		for (uint32_t i : again) passOf[i] = (uint8_t)passNo;
@@ -646,7 +689,7 @@ struct DevBatch : GaBackendBatch
 		Rl.max_slices = std::max<uint32_t>(maxRows / 64, 1);
 		Rl.arena_words = std::min<uint64_t>(64 + (uint64_t)(maxRows / 64) * (gak::kSliceHdrWords + arenaWordsPerSlice) + arenaWordsExtra, 0xfffffff0ull);
 		Rl.sparse_bw = SPARSE ? (uint32_t)std::max(std::max(L.initial_bw, L.ramp_bw), 1) : 0u;
-		SlotLayout lay = slotLayout(Rl.cap_cols, Rl.max_slices, Rl.arena_words, Rl.trace_cap, Rl.sparse_bw);
+		SlotLayout lay = slotLayout(Rl.cap_cols, Rl.max_slices, Rl.arena_words, Rl.trace_cap, Rl.sparse_bw, kWide ? sizeof(gak::WaveState<MAXN>) : 0);
 		Rl.slot_bytes = lay.bytes;
 		const uint64_t fit = scratchBudget() / lay.bytes;
 		uint32_t rslots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((uint64_t)g->cus * wavesPerCuRetry, fit), again.size()));
@@ -665,7 +708,8 @@ struct DevBatch : GaBackendBatch
 			// (the sparse method's tables are generation-stamped: they start from zero once per launch)
 			if (SPARSE) hipMemset2DAsync(scratch + lay.sparse, lay.bytes, 0, gak::sparse_mem_bytes(Rl.sparse_bw), rslots, stream);
 			hipEventRecord(evA, stream);
-			hipLaunchKernelGGL((ga_extend_kernel<MAXN, GENERAL, SPARSE>), dim3(rslots), dim3(64), 0, stream, Rl);
+			if constexpr (kWide) hipLaunchKernelGGL(ga_wide_kernel, dim3(rslots), dim3(64), 0, stream, Rl);
+			else hipLaunchKernelGGL((ga_extend_kernel<MAXN, GENERAL, SPARSE>), dim3(rslots), dim3(64), 0, stream, Rl);
 			float ms = 0;
 			rc = afterPass(ms);
 			if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d%s>: %zu jobs on %u slots, %.2f ms\n", MAXN, (int)GENERAL, SPARSE ? ",sparse" : "", again.size(), rslots, ms);
@@ -738,6 +782,14 @@ struct DevBatch : GaBackendBatch
 		rc = retryPass<64, true>(8192, 3 * 64 + 5 * 4096, 4, 8, false, true);      // only what needs the extra paths: capacity misses go straight on
 		if (rc) return rc;
 		rc = retryPass<256, true>(65536, 3 * 256 + 5 * 8192, 6, 4, true, true);
+		if (rc) return rc;
+		// bit-vector bands of more than 256 nodes (tangles of short nodes, wide bubbles, fans): 4 096 band nodes with the tables in HBM,
+		// one wave per CU, only for the jobs that overflowed the band tables or the projection heap.  A bit-vector band has at most
+		// 199 999 columns.  Arena per slice: the node table of 4 096 nodes and 32 768 columns -- four times the figure of the pass
+		// before for sixteen times its nodes, because what overflows 256 band nodes is short nodes (the passes before allow 32 columns
+		// per table node; 8 per node here), and few slices of a job are that wide.  A job that needs more reports GA_CAP_ARENA and
+		// goes on to the last pass like every other capacity miss.
+		rc = retryPass<kWideNodes, true>(kCutoffCols, 3 * (uint64_t)kWideNodes + 5 * 32768, 8, 1, true, true);
 		if (rc) return rc;
 		// bands of 200 000 cells and more (the reference's sparse method and backtrace override, ga_sparse.h): a fallback, run for the
 		// jobs that met such a band, with room for every column of every node such a slice touches

@@ -34,12 +34,35 @@ constexpr int kNbr = 4;                      // neighbours per band node cached 
 
 template <int MAXN> struct Limits
 {
-	static constexpr int kBuckets = MAXN <= 13 ? 13 : MAXN <= 29 ? 29 : MAXN <= 59 ? 59 : MAXN <= 127 ? 127 : 257;   // libstdc++ growth: 13,29,59,127,257
+	// libstdc++ growth: 13,29,59,127,257,541,1109,2357,5087
+	static constexpr int kBuckets = MAXN <= 13 ? 13 : MAXN <= 29 ? 29 : MAXN <= 59 ? 59 : MAXN <= 127 ? 127 : MAXN <= 257 ? 257 : MAXN <= 541 ? 541 : MAXN <= 1109 ? 1109 : MAXN <= 2357 ? 2357 : 5087;
 	static constexpr int kHeap = 4 * MAXN;
-	static_assert(MAXN <= 257, "bucket schedule only covers 257 band nodes");
+	// WaveState<MAXN> is some 190 bytes per band node: up to 256 nodes it is the kernel's LDS block, beyond that it lies in the wave's
+	// scratch slot in HBM (ga_device.hip: ga_wide_kernel), and hand-overs between lanes through it need ws_order / ws_handover below
+	static constexpr bool kStateInHbm = MAXN > 256;
+	static_assert(MAXN <= 5087, "bucket schedule only covers 5087 band nodes");
 };
 
-// LDS-resident per-wave state
+// ---- ordering of the hand-overs between lanes through the wave state ------------------------------------------------
+// A value that some lanes store into the state (store_lanes, scatter, a store under GA_LANE0) and other lanes then read needs an
+// ordering point in between.  A store that every lane makes with the same value needs none: each lane reads what it wrote itself.
+// ws_order: such a point where the program has always had one.  State in LDS: a single wave's LDS traffic is in order, so it only
+// stops the compiler (wave_order).  State in HBM: a workgroup-scope fence on top of that.
+// ws_handover: a hand-over that needs no marker while the state is in LDS (the compiler cannot tell the two addresses apart and
+// keeps their order); nothing at all there, ws_order with the state in HBM.
+template <int MAXN> GA_FN void ws_order()
+{
+#ifdef __HIPCC__
+	if constexpr (Limits<MAXN>::kStateInHbm) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+#endif
+	wave_order();
+}
+template <int MAXN> GA_FN void ws_handover()
+{
+	if constexpr (Limits<MAXN>::kStateInHbm) ws_order<MAXN>();
+}
+
+// per-wave state: the kernel's LDS block, or for MAXN > 256 a region of the wave's scratch slot in HBM (Limits<MAXN>::kStateInHbm)
 template <int MAXN> struct WaveState
 {
 	// previous band, in band (insertion) order
@@ -121,7 +144,7 @@ GA_FN int find_slot(const uint32_t* list, int count, uint32_t key)
 
 // ---- std::unordered_map<size_t,..> iteration order after inserting keys[0..n) one by one ----------
 // (NodeSlice.h:728-738 builds the frozen slice's map exactly so; GraphAligner.h:1117 iterates it).
-// libstdc++: identity hash, bucket = key % B, B grows 13,29,59,127,257 when size would exceed it;
+// libstdc++: identity hash, bucket = key % B, B grows 13,29,59,127,257,541,1109,2357,5087 when size would exceed it;
 // a node entering an empty bucket becomes the list head, otherwise it goes to the front of its
 // bucket's run; a rehash re-inserts the nodes in their current iteration order.
 template <int MAXN> GA_FN void hash_insert(WaveState<MAXN>& ws, const uint32_t* keys, int i, int B, int& head)
@@ -149,6 +172,7 @@ template <int MAXN> GA_FN void hash_order(WaveState<MAXN>& ws, const uint32_t* k
 	for (int i = 0; i < n; i++)
 	{
 		int grown = i == 13 ? 29 : i == 29 ? 59 : i == 59 ? 127 : i == 127 ? 257 : 0;
+		if constexpr (MAXN > 257) { if (i >= 257) grown = i == 257 ? 541 : i == 541 ? 1109 : i == 1109 ? 2357 : i == 2357 ? 5087 : 0; }
 		if (grown)
 		{
 			int k = 0;
@@ -202,9 +226,9 @@ template <int MAXN> GA_FN void hash_order_lanes(WaveState<MAXN>& ws, const uint3
 		else if (stage == 1) rank = hash_stage_rank<29>(key, m);
 		else if (stage == 2) rank = hash_stage_rank<59>(key, m);
 		else rank = hash_stage_rank<127>(key, m);
-		wave_order();
+		ws_order<MAXN>();
 		scatter(ws.h_order, rank, elem, live);
-		wave_order();
+		ws_order<MAXN>();
 		done = m;
 	}
 }
@@ -496,6 +520,7 @@ template <int MAXN> GA_FN int out_degree(const GaDevGraph& g, const WaveState<MA
 template <int MAXN> GA_FN int processing_order(const GaDevGraph& g, WaveState<MAXN>& ws, int cn)
 {
 	for (int c = 0; c < cn; c += LANES) store_lanes(ws.color + c, cn - c, VI(0));
+	ws_handover<MAXN>();                                   // color[]: stored one entry per lane, read by every lane
 	int emitted = 0;
 	for (int root = 0; root < cn; root++)
 	{
@@ -818,6 +843,7 @@ GA_FN int fill_slice(const GaDevGraph& g, WaveState<MAXN>& ws, const Slot& slot,
 			ws.cn_lastVP[s] = vp; ws.cn_lastVN[s] = vn; ws.cn_lastBefore[s] = lastBefore; ws.cn_lastExists[s] = lastExists ? 1 : 0;
 			ws.cn_min[s] = nodeMin; ws.cn_lastEnd[s] = end; ws.cn_lastEnd2[s] = end - (int)(vp >> 63) + (int)(vn >> 63);
 		}
+		ws_handover<MAXN>();                               // lane 0 stored the node's last column: every lane reads it at the node's out-neighbours
 	}
 	return GA_OK;
 }
@@ -978,7 +1004,7 @@ GA_FN GCol gcol_merge(GCol a, GCol b, const VU& lowMask, int& status)
 template <int MAXN> GA_FN int scc_order(const GaDevGraph& g, WaveState<MAXN>& ws, int cn, int& nComps)
 {
 	for (int c = 0; c < cn; c += LANES) store_lanes(ws.color + c, cn - c, VI(0));
-	wave_order();
+	ws_order<MAXN>();
 	int16_t* index = ws.h_next;
 	int16_t* tstack = ws.h_order;
 	int emitted = 0, counter = 0, tsp = 0;
@@ -1502,9 +1528,9 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 		if (st != GA_OK) return st;
 		freshCells = totalCols;
 		if (totalCols > L.cap_cols) return GA_CAP_COLS;
-		wave_order();
+		ws_order<MAXN>();
 		load_topology(g, ws, pn, cn);
-		wave_order();
+		ws_order<MAXN>();
 		// this slice's row codes normally arrived during the previous slice; request the next slice's now
 		if (rowNextSlice != slice) rowNext = load_lanes(rows + (uint64_t)slice * W, W, 0);
 		const VI rowCode = rowNext;
@@ -1520,7 +1546,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 		{
 			// a band with a cycle is filled by the confirmation-tracking path (wide kernel variants only; the
 			// narrow variant reports GA_UNSUPPORTED_CYCLE and the job is rerun by a wide one)
-			if (st == GA_UNSUPPORTED_CYCLE) { wave_order(); st = scc_order(g, ws, cn, nComps); cyclicBand = true; }
+			if (st == GA_UNSUPPORTED_CYCLE) { ws_order<MAXN>(); st = scc_order(g, ws, cn, nComps); cyclicBand = true; }
 		}
 		GA_LAP(3);
 		if (st != GA_OK) return st;
@@ -1533,7 +1559,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 			store_lanes(rec.nodes + c, cn - c, load_lanes(ws.cn_node + c, cn - c, 0));
 			store_lanes(rec.colBase + c, cn - c, load_lanes(ws.cn_colBase + c, cn - c, 0));
 		}
-		wave_order();
+		ws_order<MAXN>();
 		int minSlot;
 		uint32_t minOffset;
 		GA_LAP(0);
@@ -1546,7 +1572,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 		GA_LAP(4);
 		if (st != GA_OK) return st;
 		if (sliceMin < prevMin) return GA_ASSERTION;                              // :2469
-		wave_order();
+		ws_order<MAXN>();
 		for (int c = 0; c < cn; c += LANES) store_lanes(rec.nodeMin + c, cn - c, load_lanes(ws.cn_min + c, cn - c, 0));
 		if (GA_LANE0)
 		{
@@ -1559,7 +1585,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 	};
 	// the slice just computed becomes the state
 	auto adoptSlice = [&]() {
-		wave_order();
+		ws_order<MAXN>();
 		for (int c = 0; c < cn; c += LANES)
 		{
 			int k = cn - c;
@@ -1691,7 +1717,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 				if (GA_LANE0) slot.ckpt[nCkpt] = lastRec;                        // result.slices.push_back(lastSlice) (:2752)
 				nCkpt++;
 				closedWindow = true;
-				wave_order();
+				ws_order<MAXN>();
 			}
 			if (pushTemps) ovCount++;
 		}
@@ -1725,7 +1751,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 					}
 				}
 				if (thisMem < storeMem) { storeRec = thisRec; storeMem = thisMem; }
-				wave_order();
+				ws_order<MAXN>();
 			}
 		}
 		lastRec = thisRec;
@@ -1888,13 +1914,13 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 		uint32_t* curNodes = ws.cn_node; uint32_t* curBase = ws.cn_colBase;
 		uint32_t* prvNodes = ws.pn_node; uint32_t* prvBase = ws.pn_colBase;
 		auto loadTable = [&](uint32_t* tn, uint32_t* tb, const SliceRec& r, uint32_t n) {
-			wave_order();
+			ws_order<MAXN>();
 			for (uint32_t c = 0; c < n; c += LANES)
 			{
 				store_lanes(tn + c, (int)(n - c), load_lanes(r.nodes + c, (int)(n - c), 0));
 				store_lanes(tb + c, (int)(n - c), load_lanes(r.colBase + c, (int)(n - c), 0));
 			}
-			wave_order();
+			ws_order<MAXN>();
 		};
 		auto loadPrev = [&]() {
 			if (sIdx == 0) return;
