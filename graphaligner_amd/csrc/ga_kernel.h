@@ -1449,12 +1449,18 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 				ws.pn_outDeg[q] = 255;      // out-lists come from HBM
 			}
 		}
+		// scoreEndExists: every column of a bit-vector slice; of a sparse-method slice (hdr[11] bit 0) only the columns whose last row was
+		// written -- its untouched and partially confirmed columns have none (:2536), the frozen form keeps that bit (NodeSlice.h:370) and
+		// the record keeps it as one byte per column behind `before` (sparse_materialize)
+		const bool sparseRec = (r.hdr[11] & 1u) != 0;
+		const uint8_t* exists = (const uint8_t*)(r.before + nC);
 		for (uint32_t c = 0; c < nC; c += LANES)
 		{
 			const int k = (int)(nC - c);
 			const VU vpV = load_lanes_u64(r.vp + c, k), vnV = load_lanes_u64(r.vn + c, k);
 			const VI endV = load_lanes(r.before + c, k, 0) + vpopc(vpV) - vpopc(vnV);
-			store_lanes(slot.end_prev + c, k, (endV << 3) | 4 | vpopc(vpV & VU(1ull << 63)) | (vpopc(vnV & VU(1ull << 63)) << 1));
+			const VI existsV = sparseRec ? (load_lanes(exists + c, k, 0) << 2) : VI(4);
+			store_lanes(slot.end_prev + c, k, (endV << 3) | existsV | vpopc(vpV & VU(1ull << 63)) | (vpopc(vnV & VU(1ull << 63)) << 1));
 		}
 		pn = (int)nN; prevMin = (int)r.hdr[2];
 		union { double d; uint32_t w[2]; } a, b;

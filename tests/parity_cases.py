@@ -350,14 +350,8 @@ def case_full_size_properties(lib_path=None):
 SPARSE_FANS = [(8, 30000, 150, 600, 35, 0), (8, 30000, 400, 1000, 10, 0), (5, 50000, 100, 333, 35, 60), (12, 20000, 200, 500, 20, 45), (40, 6000, 250, 400, 35, 0)]
 
 
-def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp, lib_path=None, trace=True):
-    """bands of 200 000 cells and more: the reference leaves its bit vectors for calculateSliceAlternate (GraphAligner.h:2148-2329)
-    and keeps the window's slices to work the traceback out at once (BacktraceOverride, :167-354).  Fan graphs (synth.FanGraph): a
-    stem that ends in many long branches with a common beginning, so that the projected band holds all of them.  Reads through the
-    fan forwards (sparse slices between bit-vector ones, in both orders), with a seed past the fan (the backward part meets it from the
-    other strand: a many-to-one join), and the sharp edges the reference has here."""
-    import oracle_binding as ob
-    g = synth.FanGraph(head_len=200, stem_len=stem, n_branches=branches, branch_len=branch_len, shared=shared, seed=branches)
+def _fan_reads(g, branches, bw):
+    """the seven reads of case_sparse_method_and_override on fan `g`"""
     rng = np.random.default_rng(branches * 11 + bw)
     reads, seeds = [], []
     for k in range(4):
@@ -371,11 +365,39 @@ def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp
         pre = synth.add_errors(path[:len(g.head) + len(g.stem) + depth], 0.03, 0.03, 0.03, rng).tobytes().decode()
         post = synth.add_errors(path[len(g.head) + len(g.stem) + depth:], 0.03, 0.03, 0.03, rng).tobytes().decode()
         reads.append(pre + post); seeds.append((3 + b, len(pre), False))
+    return reads, seeds
+
+
+@functools.lru_cache(maxsize=None)
+def _fan_redos(branches, branch_len, shared, stem, bw, ramp):
+    """(redos, redos landing on a sparse slice) the oracle's slice records show for the reads of case_sparse_method_and_override
+    (redo_events.py), once per process"""
+    import redo_events
+    g = synth.FanGraph(head_len=200, stem_len=stem, n_branches=branches, branch_len=branch_len, shared=shared, seed=branches)
+    reads, seeds = _fan_reads(g, branches, bw)
+    og = ob.OracleGraph(g.nodes, g.edges)
+    seen = [redo_events.classify(og.align(r, [s], bw, ramp, record=True).pop("slice_records"), ramp) for r, s in zip(reads, seeds)]
+    return sum(c["n_redos"] for c in seen), sum(c["n_sparse_landings"] for c in seen)
+
+
+def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp, lib_path=None, trace=True):
+    """bands of 200 000 cells and more: the reference leaves its bit vectors for calculateSliceAlternate (GraphAligner.h:2148-2329)
+    and keeps the window's slices to work the traceback out at once (BacktraceOverride, :167-354).  Fan graphs (synth.FanGraph): a
+    stem that ends in many long branches with a common beginning, so that the projected band holds all of them.  Reads through the
+    fan forwards (sparse slices between bit-vector ones, in both orders), with a seed past the fan (the backward part meets it from the
+    other strand: a many-to-one join), and the sharp edges the reference has here."""
+    import oracle_binding as ob
+    g = synth.FanGraph(head_len=200, stem_len=stem, n_branches=branches, branch_len=branch_len, shared=shared, seed=branches)
+    reads, seeds = _fan_reads(g, branches, bw)
     devs, oras = pc.check_parity(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib_path, ctx="fan %d x %d bw%d/%d" % (branches, branch_len, bw, ramp), trace=trace)
     n_sparse = sum(o["sparse_slices"] for o in oras)
     n_windows = sum(o["override_traces"] for o in oras)
     n_ok = sum(1 for d in devs if d["status"] == 0 and not d["failed"])
     assert n_sparse >= 8 and n_windows >= 1 and n_ok >= 3, (n_sparse, n_windows, n_ok)
+    if ramp:
+        # reported, not asserted: these reads carry 3 % errors per kind and hardly ever go back (the redos that land on sparse
+        # slices are redo_sparse_cases.py's)
+        print("fan %d x %d bw%d/%d: the oracle saw %d redos, %d of them landing on a sparse slice" % ((branches, branch_len, bw, ramp) + _fan_redos(branches, branch_len, shared, stem, bw, ramp)))
     return devs, oras
 
 
