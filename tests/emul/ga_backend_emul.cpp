@@ -290,6 +290,23 @@ GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& flat, const GaHmmTabl
 	return g;
 }
 
+// test hook (tests/test_alphabet.py): what the host's two builders made for the batch created last -- the match words of
+// ga_batch_prepare and the row codes of buildRows -- kept only while the hook is switched on
+namespace {
+bool keepTables = false;
+std::vector<uint64_t> keptEq;
+std::vector<uint8_t> keptRows;
+std::vector<uint64_t> keptJobs;      // per job: rows_off, n_rows
+}
+extern "C" void ga_emul_keep_tables(int on) { keepTables = on != 0; keptEq.clear(); keptRows.clear(); keptJobs.clear(); }
+extern "C" void ga_emul_kept_sizes(uint64_t* out) { out[0] = keptEq.size(); out[1] = keptRows.size(); out[2] = keptJobs.size() / 2; }
+extern "C" void ga_emul_kept_copy(uint64_t* eq, uint8_t* rows, uint64_t* jobs)
+{
+	std::copy(keptEq.begin(), keptEq.end(), eq);
+	std::copy(keptRows.begin(), keptRows.end(), rows);
+	std::copy(keptJobs.begin(), keptJobs.end(), jobs);
+}
+
 GaBackendBatch* ga_backend_create_batch(GaBackendGraph* g, GaRowsProvider rows, const uint64_t* eq, const GaEqSource*, size_t eqWords, const std::vector<GaJob>& jobs, const GaRunConfig& cfg, int* status)
 {
 	EmulBatch* b = new EmulBatch();
@@ -298,6 +315,13 @@ GaBackendBatch* ga_backend_create_batch(GaBackendGraph* g, GaRowsProvider rows, 
 	b->eq.assign(eq, eq + eqWords);
 	b->jobs = jobs;
 	b->cfg = cfg;
+	if (keepTables)
+	{
+		keptEq = b->eq;
+		keptRows = rows();
+		keptJobs.clear();
+		for (const GaJob& j : jobs) { keptJobs.push_back(j.rows_off); keptJobs.push_back(j.n_rows); }
+	}
 	*status = 0;
 	return b;
 }

@@ -135,9 +135,14 @@ class OracleGraph:
             pass
 
     def align(self, seq, seeds, bw, ramp=0, record=False, name="read"):
+        """seq: str, or bytes (byte values of 128 and above as they are).  The sequence goes over as a C string: a read with a zero
+        byte cannot be given"""
         L = lib()
+        raw = seq.encode() if isinstance(seq, str) else bytes(seq)
+        if b"\0" in raw:
+            raise ValueError("a read with a zero byte cannot reach the oracle (C string)")
         sd = np.array([[s[0], s[1], int(s[2])] for s in seeds], dtype=np.int64).reshape(-1)
-        r = L.gao_align(self.h, name.encode(), seq.encode(), bw, ramp, _p(sd), len(seeds), int(record))
+        r = L.gao_align(self.h, name.encode(), raw, bw, ramp, _p(sd), len(seeds), int(record))
         try:
             return _unpack_result(L, r)
         finally:
