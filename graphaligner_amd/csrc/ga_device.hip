@@ -27,7 +27,8 @@ struct SlotLayout
 {
 	uint64_t endPrev, endCur, sliceOff, arena, trace, flags, ckpt, belowOff, sparse, ovr, state, bytes;
 };
-__host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxSlices, uint64_t arenaWords, uint32_t traceCap, uint32_t sparseBw = 0, uint64_t stateBytes = 0)
+// (sparseNodes: the band nodes of the variant whose sparse tables are laid out -- they are sized per variant, gak::SparseLimits)
+__host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxSlices, uint64_t arenaWords, uint32_t traceCap, uint32_t sparseBw = 0, uint64_t stateBytes = 0, int sparseNodes = 256)
 {
 	auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
 	SlotLayout l;
@@ -41,7 +42,7 @@ __host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxS
 	l.ckpt = at; at = up(at + 4ull * (maxSlices + 2));
 	l.belowOff = at; at = up(at + 4ull * (maxSlices + 1));
 	// the variant that carries the sparse method: its tables (first, so that the host can clear them) and the override windows
-	l.sparse = at; if (sparseBw) at = up(at + gak::sparse_mem_bytes(sparseBw));
+	l.sparse = at; if (sparseBw) at = up(at + (sparseNodes > 256 ? gak::sparse_mem_bytes<4096>(sparseBw) : gak::sparse_mem_bytes<256>(sparseBw)));
 	l.ovr = at; if (sparseBw) at = up(at + 8ull * (maxSlices + 2));
 	// the variant whose band tables do not fit in LDS: its WaveState (0 bytes for every other variant)
 	l.state = at; if (stateBytes) at = up(at + stateBytes);
@@ -109,6 +110,37 @@ __global__ void __launch_bounds__(64) ga_wide_kernel(GaLaunch L)
 		if (k >= L.n_jobs) break;                      // every wave reaches this exit once the queue is drained
 		uint32_t job = L.job_list ? L.job_list[k] : k;
 		gak::run_job<kWideNodes, true, false>(L, ws, slot, job);
+		__syncthreads();
+	}
+}
+
+// ---- bands of 200 000 cells and more with up to 4 096 nodes: the sparse method and the backtrace override (ga_sparse.h) over the
+// state in HBM.  The very last pass, for the jobs that ga_extend_kernel<256,true,true> left with GA_CAP_NODES: fans and tangles of
+// hundreds to thousands of nodes.  Launch shape, queue and state as in ga_wide_kernel; the sparse tables are those of
+// gak::SparseLimits<4096>.
+__global__ void __launch_bounds__(64) ga_wide_sparse_kernel(GaLaunch L)
+{
+	const SlotLayout lay = slotLayout(L.cap_cols, L.max_slices, L.arena_words, L.trace_cap, L.sparse_bw, sizeof(gak::WaveState<kWideNodes>), kWideNodes);
+	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.slot_bytes;
+	gak::WaveState<kWideNodes>& ws = *(gak::WaveState<kWideNodes>*)(base + lay.state);
+	gak::Slot slot;
+	slot.end_prev = (uint32_t*)(base + lay.endPrev);
+	slot.end_cur = (uint32_t*)(base + lay.endCur);
+	slot.slice_off = (uint32_t*)(base + lay.sliceOff);
+	slot.arena = (uint32_t*)(base + lay.arena);
+	slot.trace = base + lay.trace;
+	slot.slice_flags = base + lay.flags;
+	slot.ckpt = (uint32_t*)(base + lay.ckpt);
+	slot.below_off = (uint32_t*)(base + lay.belowOff);
+	slot.sparse = base + lay.sparse;
+	slot.ovr = (uint32_t*)(base + lay.ovr);
+	slot.sparse_max_bw = L.sparse_bw;
+	while (true)
+	{
+		uint32_t k = gaw::wave_atomic_add(L.next_job, 1u);
+		if (k >= L.n_jobs) break;                      // every wave reaches this exit once the queue is drained
+		uint32_t job = L.job_list ? L.job_list[k] : k;
+		gak::run_job<kWideNodes, true, true>(L, ws, slot, job);
 		__syncthreads();
 	}
 }
@@ -664,16 +696,21 @@ struct DevBatch : GaBackendBatch
 		return rc;
 	}
 
-	// (MAXN > 256: the variant with its band tables in HBM, ga_wide_kernel; it takes only the jobs whose band or projection heap overflowed)
+	// (MAXN > 256: the variants with their band tables in HBM.  ga_wide_kernel takes only the jobs whose band or projection heap
+	// overflowed; ga_wide_sparse_kernel only those that the sparse variant before it left with GA_CAP_NODES)
+	// the slots of ga_wide_sparse_kernel are some 360 MB each (arena for 2^20-column slices, 2^23 queue entries): a fallback for a few
+	// jobs, capped so that a batch of many such jobs does not claim the whole device for it
+	static constexpr uint32_t kWideSparseSlots = 32;
 	template <int MAXN, bool GENERAL, bool SPARSE = false> int retryPass(uint32_t capCols, uint64_t arenaWordsPerSlice, uint32_t traceMul, uint32_t wavesPerCuRetry, bool takeCapacity, bool takeGeneral,
 	                                                                    uint64_t arenaWordsExtra = 0)
 	{
 		constexpr bool kWide = gak::Limits<MAXN>::kStateInHbm;
-		static_assert(!kWide || (MAXN == kWideNodes && GENERAL && !SPARSE), "one variant keeps its state in HBM");
+		static_assert(!kWide || (MAXN == kWideNodes && GENERAL), "two variants keep their state in HBM: <4096,true> and <4096,true,true>");
 		std::vector<uint32_t> again;
 		for (uint32_t i : orderHost)
 		{
-			if (kWide) { if (widerTables(outs[i].status)) again.push_back(i); }
+			if (kWide && SPARSE) { if (outs[i].status == GA_CAP_NODES) again.push_back(i); }
+			else if (kWide) { if (widerTables(outs[i].status)) again.push_back(i); }
 			else if ((takeCapacity && isCapacity(outs[i].status)) || (takeGeneral && needsGeneral(outs[i].status)) || (SPARSE && outs[i].status == GA_UNSUPPORTED_BAND)) again.push_back(i);
 		}
 		if (again.empty()) return 0;
@@ -689,10 +726,11 @@ struct DevBatch : GaBackendBatch
 		Rl.max_slices = std::max<uint32_t>(maxRows / 64, 1);
 		Rl.arena_words = std::min<uint64_t>(64 + (uint64_t)(maxRows / 64) * (gak::kSliceHdrWords + arenaWordsPerSlice) + arenaWordsExtra, 0xfffffff0ull);
 		Rl.sparse_bw = SPARSE ? (uint32_t)std::max(std::max(L.initial_bw, L.ramp_bw), 1) : 0u;
-		SlotLayout lay = slotLayout(Rl.cap_cols, Rl.max_slices, Rl.arena_words, Rl.trace_cap, Rl.sparse_bw, kWide ? sizeof(gak::WaveState<MAXN>) : 0);
+		SlotLayout lay = slotLayout(Rl.cap_cols, Rl.max_slices, Rl.arena_words, Rl.trace_cap, Rl.sparse_bw, kWide ? sizeof(gak::WaveState<MAXN>) : 0, MAXN);
 		Rl.slot_bytes = lay.bytes;
 		const uint64_t fit = scratchBudget() / lay.bytes;
 		uint32_t rslots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((uint64_t)g->cus * wavesPerCuRetry, fit), again.size()));
+		if (kWide && SPARSE) rslots = std::min(rslots, kWideSparseSlots);
 		if (knobs.waveSlots) rslots = std::min(rslots, knobs.waveSlots);
 		bool fromPool = false;
 		uint8_t* scratch = takeScratch((size_t)rslots * lay.bytes, fromPool);
@@ -706,13 +744,28 @@ struct DevBatch : GaBackendBatch
 		{
 			hipMemsetAsync(Rl.next_job, 0, 16, stream);
 			// (the sparse method's tables are generation-stamped: they start from zero once per launch)
-			if (SPARSE) hipMemset2DAsync(scratch + lay.sparse, lay.bytes, 0, gak::sparse_mem_bytes(Rl.sparse_bw), rslots, stream);
+			if constexpr (kWide && SPARSE)
+			{
+				// (slot by slot: the tables of this variant are some 160 MB of a 360 MB slot; without them cleared nothing is launched)
+				for (uint32_t s = 0; s < rslots && !rc; s++)
+					if (hipMemsetAsync(scratch + (uint64_t)s * lay.bytes + lay.sparse, 0, gak::sparse_mem_bytes<MAXN>(Rl.sparse_bw), stream) != hipSuccess) rc = GA_E_DEVICE;
+			}
+			else if (SPARSE) hipMemset2DAsync(scratch + lay.sparse, lay.bytes, 0, gak::sparse_mem_bytes<MAXN>(Rl.sparse_bw), rslots, stream);
+		}
+		if (!rc)
+		{
 			hipEventRecord(evA, stream);
-			if constexpr (kWide) hipLaunchKernelGGL(ga_wide_kernel, dim3(rslots), dim3(64), 0, stream, Rl);
+			if constexpr (kWide && SPARSE) hipLaunchKernelGGL(ga_wide_sparse_kernel, dim3(rslots), dim3(64), 0, stream, Rl);
+			else if constexpr (kWide) hipLaunchKernelGGL(ga_wide_kernel, dim3(rslots), dim3(64), 0, stream, Rl);
 			else hipLaunchKernelGGL((ga_extend_kernel<MAXN, GENERAL, SPARSE>), dim3(rslots), dim3(64), 0, stream, Rl);
 			float ms = 0;
 			rc = afterPass(ms);
-			if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d%s>: %zu jobs on %u slots, %.2f ms\n", MAXN, (int)GENERAL, SPARSE ? ",sparse" : "", again.size(), rslots, ms);
+			if (knobs.debugPasses)
+			{
+				size_t capNodes = 0;
+				for (uint32_t i : again) if (outs[i].status == GA_CAP_NODES) capNodes++;
+				fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d%s>: %zu jobs on %u slots, %.2f ms, %zu left with GA_CAP_NODES\n", MAXN, (int)GENERAL, SPARSE ? ",sparse" : "", again.size(), rslots, ms, capNodes);
+			}
 		}
 		if (fromPool) g->givePool();
 		return rc;
@@ -795,6 +848,12 @@ struct DevBatch : GaBackendBatch
 		// jobs that met such a band, with room for every column of every node such a slice touches
 		// (also the last resort for what the passes before could not hold: bit-vector bands may have up to 199 999 columns)
 		rc = retryPass<256, true, true>(1u << 20, 3 * 256 + 5 * 20000, 8, 1, true, true, 48ull << 20);
+		if (rc) return rc;
+		// such bands with more than 256 nodes (fans and tangles of hundreds to thousands of nodes): the same with 4 096 band nodes, the
+		// state in HBM and tables sized for it, only for the jobs the pass above left with GA_CAP_NODES -- the other capacity misses of
+		// that pass (its row set, its touched columns, the arena, the trace) keep their status.  Arena as above: room for every column
+		// of every node a sparse slice touches, 2^20 columns.  No such job, no launch.
+		rc = retryPass<kWideNodes, true, true>(1u << 20, 3 * (uint64_t)kWideNodes + 5 * 20000, 8, 1, true, true, 48ull << 20);
 		for (int k = 0; k < 8; k++) { st.stamps[k] = 0; for (auto& o : outs) st.stamps[k] += o.stamps[k]; }
 		return rc;
 	}

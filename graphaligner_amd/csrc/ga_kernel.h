@@ -38,7 +38,7 @@ template <int MAXN> struct Limits
 	static constexpr int kBuckets = MAXN <= 13 ? 13 : MAXN <= 29 ? 29 : MAXN <= 59 ? 59 : MAXN <= 127 ? 127 : MAXN <= 257 ? 257 : MAXN <= 541 ? 541 : MAXN <= 1109 ? 1109 : MAXN <= 2357 ? 2357 : 5087;
 	static constexpr int kHeap = 4 * MAXN;
 	// WaveState<MAXN> is some 190 bytes per band node: up to 256 nodes it is the kernel's LDS block, beyond that it lies in the wave's
-	// scratch slot in HBM (ga_device.hip: ga_wide_kernel), and hand-overs between lanes through it need ws_order / ws_handover below
+	// scratch slot in HBM (ga_device.hip: ga_wide_kernel, ga_wide_sparse_kernel), and hand-overs between lanes through it need ws_order / ws_handover below
 	static constexpr bool kStateInHbm = MAXN > 256;
 	static_assert(MAXN <= 5087, "bucket schedule only covers 5087 band nodes");
 };
@@ -1397,7 +1397,7 @@ template <int MAXN, bool GENERAL, bool SPARSE = false>
 GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, uint32_t jobIndex)
 {
 	constexpr bool kWide = GENERAL;             // cycles and ramp redos: compiled into the general variants only
-	constexpr bool kSparse = SPARSE && GENERAL; // bands of >= 200 000 cells (sparse method, backtrace override): the last variant of the ladder only
+	constexpr bool kSparse = SPARSE && GENERAL; // bands of >= 200 000 cells (sparse method, backtrace override): the last two variants of the ladder only
 	const GaDevGraph& g = L.graph;
 	const GaJob job = L.jobs[jobIndex];
 	const GaHmmTables& hmm = *L.hmm;
@@ -1505,7 +1505,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 				// ---- the band has 200 000 cells or more: the sparse method (pickMethodAndExtendFill, :2499-2520) ----
 				wave_sync();
 				if ((uint32_t)bandwidth > slot.sparse_max_bw) return GA_CAP_HEAP;
-				const SparseMem sm = sparse_mem_at(slot.sparse, slot.sparse_max_bw);
+				const SparseMem sm = sparse_mem_at<MAXN>(slot.sparse, slot.sparse_max_bw);
 				const SparseResult sr = sparse_fill(g, ws, slot, sm, rows + (uint64_t)slice * W, job.n_rows, slice * W, pn, prevMin, bandwidth, cn);
 				rowNextSlice = 0xffffffffu;                                           // (the row codes were not taken from the prefetch)
 				if (sr.status != GA_OK) return sr.status;
@@ -1531,6 +1531,9 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 				return GA_OK;
 			}
 		}
+		// (in the variants of the last two passes a projection heap that overflows is reported as what it is there, band tables too small
+		// for the band: the pass with 4 096 band nodes takes GA_CAP_NODES and leaves GA_CAP_HEAP, which the sparse method's own tables report)
+		if constexpr (kSparse) { if (st == GA_CAP_HEAP) st = GA_CAP_NODES; }
 		if (st != GA_OK) return st;
 		freshCells = totalCols;
 		if (totalCols > L.cap_cols) return GA_CAP_COLS;
@@ -1630,7 +1633,7 @@ GA_FN void run_job(const GaLaunch& L, WaveState<MAXN>& ws, const Slot& slotIn, u
 		{
 			if (ovCount == 0 || lastRec == kSeedRecord || recSlice(lastRec) != ovFirst + ovCount - 1) return GA_ASSERTION;   // assert(lastSlice.j == backtraceOverrideTemps.back().j)
 			wave_sync();
-			const SparseMem sm = sparse_mem_at(slot.sparse, slot.sparse_max_bw);
+			const SparseMem sm = sparse_mem_at<MAXN>(slot.sparse, slot.sparse_max_bw);
 			const int st = explore_override(g, ws, slot, sm, slot.slice_off, ovFirst, ovCount, ovPreRec == kSeedRecord ? 0u : ovPreRec, ovPreRec == kSeedRecord,
 			                                job.seed_node, rows, (int)job.n_rows);
 			if (st != GA_OK) return st;

@@ -2,7 +2,8 @@
 // (calculateSliceAlternate / setValue / finalizeAlternateSlice, GraphAligner.h:2148-2329, 2130-2146, 2523-2552; WordSlice.h:231-337)
 // and what the backtrace override (:167-354) adds to a traceback that already keeps every slice.
 //
-// Included by ga_kernel.h (namespace gak); compiled into the last kernel of the ladder only.  This is a fallback: a band that wide
+// Included by ga_kernel.h (namespace gak); compiled into the last two kernels of the ladder only (256 band nodes in LDS, then 4 096 with
+// the state in HBM and the larger tables of SparseLimits<4096>).  This is a fallback: a band that wide
 // is a tangle, or a fan of long nodes, and the reference itself leaves its bit vectors for a cell-by-cell bucket queue there.  The
 // queue's ORDER is part of the result (the first touch of a node decides the slice's node order and with it the next slice's map
 // order; the last entry of the final bucket is where the traceback starts), so the queue is run as what it is: a sequential program,
@@ -14,27 +15,43 @@
 
 namespace gak {
 
-constexpr uint32_t kSetSize = 1u << 14;          // cells processed in one row (open addressing, generation-stamped)
-constexpr uint32_t kMapSize = 1u << 17;          // (node slot, offset) -> touched word
-constexpr uint32_t kSparseWords = 1u << 16;      // touched words per slice
-constexpr uint32_t kSparseEntries = 1u << 19;    // queue entries per row set, shared evenly by the bandwidth + 1 buckets
+// table sizes per variant.  MAXN <= 256 (ga_extend_kernel<256,true,true>): what that variant has always had -- its layout and its
+// capacity misses are pinned by tests.  MAXN > 256 (ga_wide_sparse_kernel): a fan or tangle of thousands of short nodes puts up to
+// ~63 000 cells into one row and touches up to ~86 000 columns (measured on the oracle): 2^17 cells per row (the
+// row set is kept at most half full), 2^18 touched columns, the queue and the map in proportion, and hashed node -> slot tables.
+template <int MAXN> struct SparseLimits
+{
+	static constexpr bool kBig = MAXN > 256;
+	static constexpr uint32_t kSetSize = kBig ? 1u << 18 : 1u << 14;          // cells processed in one row (open addressing, generation-stamped), at most half full
+	static constexpr uint32_t kMapSize = kBig ? 1u << 19 : 1u << 17;          // (node slot, offset) -> touched word
+	static constexpr uint32_t kSparseWords = kBig ? 1u << 18 : 1u << 16;      // touched words per slice; also bounds the work lists (seeds, the override's cells)
+	static constexpr uint32_t kSparseEntries = kBig ? 1u << 23 : 1u << 19;    // queue entries per row set, shared evenly by the bandwidth + 1 buckets
+	// node -> slot tables (open addressing, generation-stamped, at most a quarter full): one for the slice being filled, two for the
+	// records the override walks.  0: the variant scans its node lists (at most 256 entries) as it always has
+	static constexpr uint32_t kNodeMap = kBig ? 4u * (uint32_t)MAXN : 0u;
+	static constexpr uint32_t kNodeTabs = 2;
+	static_assert((kNodeMap & (kNodeMap - 1)) == 0, "table sizes are powers of two");
+};
 
 struct SparseMem
 {
-	uint32_t* gen;        // [4] running generation numbers of the two tables (kept across the slot's jobs; zeroed by the host at launch)
+	uint32_t* gen;        // [4] running generation numbers of the tables: [0] row set, [1] map, [2] node tables (kept across the slot's jobs; zeroed by the host at launch)
 	uint32_t* cnt;        // [2][nb] entries per bucket
 	uint64_t* ent;        // [2][kSparseEntries] node << 32 | offset inside the node
 	uint64_t* setKey; uint32_t* setGen;                       // [kSetSize]
 	uint64_t* mapKey; uint32_t* mapGen; uint32_t* mapVal;     // [kMapSize]
 	uint64_t* wVp; uint64_t* wVn; int32_t* wBefore; int32_t* wEnd; uint32_t* wSlot; uint32_t* wOff; uint32_t* wRows;   // [kSparseWords]
 	uint32_t* list;       // [2 * kSparseWords] work lists (usable end cells of the previous slice; the override's reachable cells)
+	uint32_t* nodeKey; uint32_t* nodeGen; uint32_t* nodeVal;  // [kNodeTabs][kNodeMap] node -> slot (variants with kNodeMap > 0 only)
 };
-inline
+template <int MAXN> inline
 #ifndef GA_EMULATE
 __host__ __device__
 #endif
 uint64_t sparse_mem_bytes(uint32_t maxBandwidth)
 {
+	constexpr uint32_t kSparseEntries = SparseLimits<MAXN>::kSparseEntries, kSetSize = SparseLimits<MAXN>::kSetSize, kMapSize = SparseLimits<MAXN>::kMapSize,
+	                   kSparseWords = SparseLimits<MAXN>::kSparseWords;
 	auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
 	uint64_t at = 256;
 	at += up(8ull * ((uint64_t)maxBandwidth + 1));
@@ -43,14 +60,23 @@ uint64_t sparse_mem_bytes(uint32_t maxBandwidth)
 	at += up(16ull * kMapSize);
 	at += up(36ull * kSparseWords);
 	at += up(8ull * kSparseWords);
+	at += up(12ull * SparseLimits<MAXN>::kNodeTabs * SparseLimits<MAXN>::kNodeMap);      // (0 bytes for MAXN <= 256: that variant's layout is what it was)
 	return at;
 }
+// (without a variant: the tables of MAXN <= 256)
 inline
+#ifndef GA_EMULATE
+__host__ __device__
+#endif
+uint64_t sparse_mem_bytes(uint32_t maxBandwidth) { return sparse_mem_bytes<256>(maxBandwidth); }
+template <int MAXN> inline
 #ifndef GA_EMULATE
 __host__ __device__
 #endif
 SparseMem sparse_mem_at(uint8_t* base, uint32_t maxBandwidth)
 {
+	constexpr uint32_t kSparseEntries = SparseLimits<MAXN>::kSparseEntries, kSetSize = SparseLimits<MAXN>::kSetSize, kMapSize = SparseLimits<MAXN>::kMapSize,
+	                   kSparseWords = SparseLimits<MAXN>::kSparseWords, kNodeWords = SparseLimits<MAXN>::kNodeTabs * SparseLimits<MAXN>::kNodeMap;
 	auto up = [](uint64_t x) { return (x + 255) & ~255ull; };
 	SparseMem m;
 	uint64_t at = 0;
@@ -61,7 +87,8 @@ SparseMem sparse_mem_at(uint8_t* base, uint32_t maxBandwidth)
 	m.mapKey = (uint64_t*)(base + at); m.mapGen = (uint32_t*)(base + at + 8ull * kMapSize); m.mapVal = m.mapGen + kMapSize; at += up(16ull * kMapSize);
 	m.wVp = (uint64_t*)(base + at); m.wVn = m.wVp + kSparseWords; m.wBefore = (int32_t*)(m.wVn + kSparseWords); m.wEnd = m.wBefore + kSparseWords;
 	m.wSlot = (uint32_t*)(m.wEnd + kSparseWords); m.wOff = m.wSlot + kSparseWords; m.wRows = m.wOff + kSparseWords; at += up(36ull * kSparseWords);
-	m.list = (uint32_t*)(base + at);
+	m.list = (uint32_t*)(base + at); at += up(8ull * kSparseWords);
+	m.nodeKey = (uint32_t*)(base + at); m.nodeGen = m.nodeKey + kNodeWords; m.nodeVal = m.nodeGen + kNodeWords;
 	return m;
 }
 
@@ -80,6 +107,33 @@ struct SparseResult
 };
 
 GA_FN uint32_t mix64(uint64_t k) { k ^= k >> 29; k *= 0x9e3779b97f4a7c15ull; k ^= k >> 32; return (uint32_t)k; }
+
+// ---- node -> slot without a scan (lane 0; variants with SparseLimits<MAXN>::kNodeMap > 0) --------------------------------------------
+// With thousands of nodes in a slice, a scan of the node list is thousands of dependent HBM loads per cell.  One table of kNodeMap
+// entries, open addressing with linear probing, an entry is live while its stamp is the table's: starting a table anew is one
+// increment of the running generation (sm.gen[2]), as for the row set and the map.  The table only answers "which slot"; the slots
+// themselves are still handed out in first-touch order by the caller.
+struct NodeTab { uint32_t* key; uint32_t* gen; uint32_t* val; uint32_t stamp; uint32_t mask; };
+GA_FN NodeTab node_tab(const SparseMem& sm, uint32_t which, uint32_t size, uint32_t stamp)
+{
+	NodeTab t;
+	t.key = sm.nodeKey + (uint64_t)which * size; t.gen = sm.nodeGen + (uint64_t)which * size; t.val = sm.nodeVal + (uint64_t)which * size;
+	t.stamp = stamp; t.mask = size - 1;
+	return t;
+}
+GA_FN int node_tab_find(const NodeTab& t, uint32_t node)
+{
+	uint32_t h = mix64(node) & t.mask;
+	while (t.gen[h] == t.stamp) { if (t.key[h] == node) return (int)t.val[h]; h = (h + 1) & t.mask; }
+	return -1;
+}
+// (the node is not in the table, and the table is never full: at most MAXN of its 4 * MAXN entries are live)
+GA_FN void node_tab_put(const NodeTab& t, uint32_t node, uint32_t slotN)
+{
+	uint32_t h = mix64(node) & t.mask;
+	while (t.gen[h] == t.stamp) h = (h + 1) & t.mask;
+	t.key[h] = node; t.val[h] = slotN; t.gen[h] = t.stamp;
+}
 
 // WordSlice::setValue on a touched word (WordSlice.h:231-337); rows = confirmedRows.rows | partial << 8
 GA_FN int sparse_set_value(uint64_t& vp, uint64_t& vn, int& before, int& end, uint32_t& rowsWord, int row, int value)
@@ -144,6 +198,8 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 	res.status = GA_OK; res.minScore = 0; res.minSlot = 0; res.minOffset = 0; res.nWords = 0; res.numCells = 0;
 	res.endsTooFar = false; res.beforeTooFar = false; res.oddWord = false;
 	cnOut = 0;
+	constexpr uint32_t kSparseEntries = SparseLimits<MAXN>::kSparseEntries, kSetSize = SparseLimits<MAXN>::kSetSize, kMapSize = SparseLimits<MAXN>::kMapSize,
+	                   kSparseWords = SparseLimits<MAXN>::kSparseWords, kNodeMap = SparseLimits<MAXN>::kNodeMap;
 	// (:2220 indexes calculables[1] of a one-element vector when the bandwidth is 0 -- slice 0 of a run without a ramp width: undefined
 	// behaviour in the reference, reported as an assertion)
 	if (bandwidth < 1) { res.status = GA_ASSERTION; return res; }
@@ -192,6 +248,13 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 	if (GA_LANE0)
 	{
 		uint32_t setGen = sm.gen[0], mapGen = sm.gen[1] + 1;
+		// the touched nodes' slots: a scan of cn_node for up to 256 nodes, a hashed table beyond (first-touch order is the caller's either way)
+		NodeTab tab = node_tab(sm, 0, kNodeMap, 0);
+		if constexpr (kNodeMap != 0) { tab.stamp = sm.gen[2] + 1; sm.gen[2] = tab.stamp; }
+		auto slotOf = [&](uint32_t node) -> int {
+			if constexpr (kNodeMap != 0) return node_tab_find(tab, node);
+			else { for (int t = 0; t < cn; t++) if (ws.cn_node[t] == node) return t; return -1; }
+		};
 		uint32_t* cntNow = sm.cnt;
 		uint32_t* cntNext = sm.cnt + nb;
 		uint64_t* entNow = sm.ent;
@@ -205,14 +268,17 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 			cnt[bucket] = c + 1;
 		};
 		// a node's record, remembered for the cells that follow in the same node
-		uint32_t recNode = 0xffffffffu, recLen = 0, recOutDeg = 0, recOut[4] = {0, 0, 0, 0};
+		// (the cached out-neighbours are four scalars picked by comparison: an array indexed by the loop counter would be the kernel's
+		// only private-segment object)
+		uint32_t recNode = 0xffffffffu, recLen = 0, recOutDeg = 0, recOut0 = 0, recOut1 = 0, recOut2 = 0, recOut3 = 0;
 		uint64_t recFirst = 0;
 		auto nodeInfo = [&](uint32_t node) {
 			if (node == recNode) return;
 			const uint32_t* r = g.node_rec + (uint64_t)node * GA_NODE_REC_WORDS;
 			recNode = node; recFirst = ((uint64_t)r[1] << 32) | r[0]; recLen = r[2]; recOutDeg = r[3] >> 16;
-			for (int e = 0; e < 4; e++) recOut[e] = r[4 + e];
+			recOut0 = r[4]; recOut1 = r[5]; recOut2 = r[6]; recOut3 = r[7];
 		};
+		auto recOut = [&](uint32_t e) { return e == 0 ? recOut0 : e == 1 ? recOut1 : e == 2 ? recOut2 : recOut3; };
 		auto matchAt = [&](int row, uint64_t column) { return ((rows[row] >> g_base(g, column)) & 1) != 0; };
 		auto firstColOf = [&](uint32_t node) { const uint32_t* r = g.node_rec + (uint64_t)node * GA_NODE_REC_WORDS; return ((uint64_t)r[1] << 32) | r[0]; };
 		// ---- row j from the previous slice (:2163-2219) ----
@@ -235,7 +301,7 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 					const uint32_t deg = recOutDeg;
 					for (uint32_t e = 0; e < deg && status == GA_OK; e++)
 					{
-						const uint32_t nbr = deg <= 4 ? recOut[e] : g.out_nbr[g.out_off[node] + e];
+						const uint32_t nbr = deg <= 4 ? recOut(e) : g.out_nbr[g.out_off[node] + e];
 						push(cntNow, entNow, rel + (matchAt(0, firstColOf(nbr)) ? 0 : 1), nbr, 0);
 					}
 				}
@@ -277,12 +343,13 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 					if (node == lastSlotNode) slotN = lastSlot;
 					else
 					{
-						for (int t = 0; t < cn; t++) if (ws.cn_node[t] == node) { slotN = t; break; }
+						slotN = slotOf(node);
 						if (slotN < 0)
 						{
 							if (cn >= MAXN) { status = GA_CAP_NODES; break; }
 							slotN = cn++;
 							ws.cn_node[slotN] = node; ws.cn_len[slotN] = recLen; ws.st_cur[slotN] = 0;
+							if constexpr (kNodeMap != 0) node_tab_put(tab, node, (uint32_t)slotN);
 							numCells += recLen;
 						}
 						lastSlotNode = node; lastSlot = slotN;
@@ -318,7 +385,7 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 						const uint32_t deg = recOutDeg;
 						for (uint32_t e = 0; e < deg && status == GA_OK; e++)
 						{
-							const uint32_t nbr = deg <= 4 ? recOut[e] : g.out_nbr[g.out_off[node] + e];
+							const uint32_t nbr = deg <= 4 ? recOut(e) : g.out_nbr[g.out_off[node] + e];
 							onward(nbr, 0, firstColOf(nbr));
 						}
 					}
@@ -343,8 +410,7 @@ GA_FN SparseResult sparse_fill(const GaDevGraph& g, WaveState<MAXN>& ws, const S
 			{
 				const uint64_t key = entNow[(uint64_t)bucket * capB + cntNow[bucket] - 1];
 				minOffset = (uint32_t)key;
-				minSlot = -1;
-				for (int t = 0; t < cn; t++) if (ws.cn_node[t] == (uint32_t)(key >> 32)) { minSlot = t; break; }
+				minSlot = slotOf((uint32_t)(key >> 32));
 				if (minSlot < 0) status = GA_ASSERTION;
 			}
 		}
@@ -463,7 +529,8 @@ GA_FN void sparse_materialize(const GaDevGraph& g, WaveState<MAXN>& ws, const Sl
 // program keeps every slice, so its traceback needs no links; what remains of the override is (a) the traceback's own rule inside a
 // window it uses -- a cell in a slice's last row must exist (:211, :202-209), enforced in run_job -- and (b) that pickBacktracePredecessor
 // asserts on EVERY reachable cell, on the path or not.  (b) is this function: the same walk, lane 0, cell by cell.
-struct RecView { const uint32_t* nodes; const uint32_t* colBase; uint32_t nNodes; const uint64_t* vp; const uint64_t* vn; const int32_t* before; const uint8_t* exists; };
+// (tab: the record's node -> slot table, for the variants that keep one -- HASHED below; the others scan `nodes`)
+struct RecView { const uint32_t* nodes; const uint32_t* colBase; uint32_t nNodes; const uint64_t* vp; const uint64_t* vn; const int32_t* before; const uint8_t* exists; NodeTab tab; };
 GA_FN RecView rec_view(uint32_t* arena, uint32_t off)
 {
 	RecView v;
@@ -471,9 +538,14 @@ GA_FN RecView rec_view(uint32_t* arena, uint32_t off)
 	const SliceRec r = slice_at(arena, off, nN, nC);
 	v.nodes = r.nodes; v.colBase = r.colBase; v.nNodes = nN; v.vp = r.vp; v.vn = r.vn; v.before = r.before;
 	v.exists = (const uint8_t*)(r.before + nC);
+	v.tab.key = nullptr; v.tab.gen = nullptr; v.tab.val = nullptr; v.tab.stamp = 0; v.tab.mask = 0;
 	return v;
 }
-GA_FN int view_slot(const RecView& v, uint32_t node) { for (uint32_t t = 0; t < v.nNodes; t++) if (v.nodes[t] == node) return (int)t; return -1; }
+template <bool HASHED> GA_FN int view_slot(const RecView& v, uint32_t node)
+{
+	if constexpr (HASHED) return node_tab_find(v.tab, node);
+	else { for (uint32_t t = 0; t < v.nNodes; t++) if (v.nodes[t] == node) return (int)t; return -1; }
+}
 GA_FN int view_value(const RecView& v, int slotN, uint32_t off, int row)
 {
 	const uint32_t idx = v.colBase[slotN] + off;
@@ -483,24 +555,25 @@ GA_FN int view_value(const RecView& v, int slotN, uint32_t off, int row)
 
 // predecessor of (node, off, r) in the slice `cur` (r = row inside the slice); `above` = the slice before it (seedAbove: that is the
 // all-zero seed slice).  Returns 0 left, 1 diagonal, 2 up, < 0 an assertion; the cell entered in pn / po.
+template <bool HASHED>
 GA_FN int pick_pred_scalar(const GaDevGraph& g, const RecView& cur, const RecView& above, bool seedAbove, uint32_t seedNode, const uint8_t* rowCodes,
                            uint32_t globalRow, int big, uint32_t node, uint32_t off, int r, uint32_t& pn, uint32_t& po, bool& freeStart)
 {
 	freeStart = false;
-	const int sl = view_slot(cur, node);
+	const int sl = view_slot<HASHED>(cur, node);
 	if (sl < 0) return -1;                                                                  // assert(slice.scores.hasNode(nodeIndex)) (:498)
 	const int here = view_value(cur, sl, off, r);
 	auto aboveValue = [&](uint32_t n, uint32_t o) -> int {
 		if (seedAbove) return n == seedNode ? 0 : big;
-		const int t = view_slot(above, n);
+		const int t = view_slot<HASHED>(above, n);
 		return t < 0 ? big : view_value(above, t, o, W - 1);
 	};
-	if (globalRow == 0 && (seedAbove ? node == seedNode : view_slot(above, node) >= 0) && (here == 0 || here == 1)) { freeStart = true; pn = node; po = off; return 2; }   // :500
+	if (globalRow == 0 && (seedAbove ? node == seedNode : view_slot<HASHED>(above, node) >= 0) && (here == 0 || here == 1)) { freeStart = true; pn = node; po = off; return 2; }   // :500
 	const uint32_t* rec = g.node_rec + (uint64_t)node * GA_NODE_REC_WORDS;
 	const uint64_t column = (((uint64_t)rec[1] << 32) | rec[0]) + off;
 	const bool match = ((rowCodes[globalRow] >> g_base(g, column)) & 1) != 0;
 	auto tryFrom = [&](uint32_t un, uint32_t uo, int& out) -> bool {
-		const int t = view_slot(cur, un);
+		const int t = view_slot<HASHED>(cur, un);
 		const int horizontal = t < 0 ? big : view_value(cur, t, uo, r);
 		if (horizontal < here - 1) { out = -1; return true; }
 		if (horizontal == here - 1) { pn = un; po = uo; out = 0; return true; }
@@ -534,6 +607,8 @@ template <int MAXN>
 GA_FN int explore_override(const GaDevGraph& g, WaveState<MAXN>& ws, const Slot& slot, const SparseMem& sm, const uint32_t* sliceOff, uint32_t firstSlice, uint32_t count,
                            uint32_t preRec, bool preIsSeed, uint32_t seedNode, const uint8_t* rowCodes, int big)
 {
+	constexpr uint32_t kSetSize = SparseLimits<MAXN>::kSetSize, kSparseWords = SparseLimits<MAXN>::kSparseWords, kNodeMap = SparseLimits<MAXN>::kNodeMap;
+	constexpr bool kHashed = kNodeMap != 0;
 	const VI lane = lane_iota();
 	// the existing end cells of the window's last slice, in the record's order (the order does not matter: every cell is visited once)
 	const uint32_t lastOff = sliceOff[firstSlice + count - 1];
@@ -589,14 +664,36 @@ GA_FN int explore_override(const GaDevGraph& g, WaveState<MAXN>& ws, const Slot&
 		};
 		for (uint32_t q = 0; q < nCur; q++) visit(nRowsWin - 1, cur[2 * q], cur[2 * q + 1]);
 		uint32_t live = nCur;                          // entries of the two rows in the table (bounded well below its size)
+		// node -> slot of the two records a row looks at (the slice it lies in, the slice above): one table each, filled from the record's
+		// node list when the walk first needs it -- once per slice of the window, since the slice above becomes the slice walked
+		uint32_t nodeGen = kHashed ? sm.gen[2] : 0u;
+		uint32_t tabRec0 = 0xffffffffu, tabRec1 = 0xffffffffu, tabStamp0 = 0, tabStamp1 = 0;      // which record each table holds, and under which stamp
+		auto attachTab = [&](RecView& v, uint32_t recOff, uint32_t keepRec) {
+			if constexpr (kHashed)
+			{
+				if (tabRec0 != recOff && tabRec1 != recOff)
+				{
+					// (into the table that does not hold the other record of this row)
+					const bool second = tabRec0 == keepRec && keepRec != 0xffffffffu;
+					const uint32_t stamp = ++nodeGen;
+					if (second) { tabRec1 = recOff; tabStamp1 = stamp; } else { tabRec0 = recOff; tabStamp0 = stamp; }
+					const NodeTab t = node_tab(sm, second ? 1u : 0u, kNodeMap, stamp);
+					for (uint32_t q = 0; q < v.nNodes; q++) node_tab_put(t, v.nodes[q], q);
+				}
+				v.tab = tabRec0 == recOff ? node_tab(sm, 0u, kNodeMap, tabStamp0) : node_tab(sm, 1u, kNodeMap, tabStamp1);
+			}
+		};
 		for (uint32_t row = nRowsWin; row-- > 0 && status == GA_OK;)
 		{
 			const uint32_t si = row / W;
 			const int r = (int)(row % W);
-			const RecView view = rec_view(slot.arena, sliceOff[firstSlice + si]);
+			const uint32_t viewOff = sliceOff[firstSlice + si];
+			RecView view = rec_view(slot.arena, viewOff);
 			const bool seedAbove = si == 0 && preIsSeed;
+			const uint32_t aboveOff = seedAbove ? 0xffffffffu : (si > 0 ? sliceOff[firstSlice + si - 1] : preRec);
+			attachTab(view, viewOff, aboveOff);
 			RecView above = view;
-			if (!(si == 0 && preIsSeed)) above = rec_view(slot.arena, si > 0 ? sliceOff[firstSlice + si - 1] : preRec);
+			if (!seedAbove) { above = rec_view(slot.arena, aboveOff); attachTab(above, aboveOff, viewOff); }
 			const uint32_t globalRow = (firstSlice + si) * W + (uint32_t)r;
 			liveA = gen + 1 + row; liveB = row > 0 ? gen + row : liveA;
 			nNxt = 0;
@@ -606,13 +703,13 @@ GA_FN int explore_override(const GaDevGraph& g, WaveState<MAXN>& ws, const Slot&
 				if (row > 0 && r == W - 1)
 				{
 					// a cell without an end score is registered and not followed (:243-250)
-					const int t = view_slot(view, node);
+					const int t = view_slot<kHashed>(view, node);
 					if (t < 0) { status = GA_ASSERTION; break; }
 					if (view.exists[view.colBase[t] + off] == 0) continue;
 				}
 				uint32_t pn2 = 0, po2 = 0;
 				bool freeStart = false;
-				const int res = pick_pred_scalar(g, view, above, seedAbove, seedNode, rowCodes, globalRow, big, node, off, r, pn2, po2, freeStart);
+				const int res = pick_pred_scalar<kHashed>(g, view, above, seedAbove, seedNode, rowCodes, globalRow, big, node, off, r, pn2, po2, freeStart);
 				if (res < 0) { status = GA_ASSERTION; break; }
 				if (res == 0)
 				{
@@ -636,6 +733,7 @@ GA_FN int explore_override(const GaDevGraph& g, WaveState<MAXN>& ws, const Slot&
 			nCur = nNxt;
 		}
 		sm.gen[0] = gen + 1 + nRowsWin + 1;
+		if constexpr (kHashed) sm.gen[2] = nodeGen;
 	}
 	wave_sync();
 	(void)ws;

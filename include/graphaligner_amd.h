@@ -46,11 +46,12 @@ typedef enum ga_status {
 	                               last kernel variant, which carries that method and the backtrace override -- returned only when that pass
 	                               could not get its device memory */
 	GA_S_BAD_SEED = 3,          /* seed node id unknown: std::out_of_range in the reference (GraphAligner.h:423) */
-	GA_S_CAPACITY = 10,         /* device buffers too small even after the automatic retry: a bit-vector band (< 200 000 cells) of more than
-	                             * 4 096 nodes, or whose projection heap needs more than 16 384 entries; a sparse band (>= 200 000 cells) of more
-	                             * than 256 nodes, or with more than 8 192 cells within the bandwidth in one row (e.g. 40 long branches met at a ramp
-	                             * width of 70), or of more than 65 536 touched columns; a traceback move into an in-neighbour whose ordinal in the
-	                             * node's in-list is above 62 */
+	GA_S_CAPACITY = 10,         /* device buffers too small even after the automatic retry: a band of more than 4 096 nodes, bit-vector
+	                             * (< 200 000 cells) or sparse (>= 200 000 cells), or whose projection heap needs more than 16 384 entries; a
+	                             * sparse band of up to 256 nodes with more than 8 192 cells within the bandwidth in one row (e.g. 40 long
+	                             * branches met at a ramp width of 70) or more than 65 536 touched columns; a sparse band of 257 to 4 096 nodes
+	                             * with more than 131 072 such cells in one row or more than 262 144 touched columns; a traceback move into an
+	                             * in-neighbour whose ordinal in the node's in-list is above 62 */
 	GA_S_UNSUPPORTED_CYCLE = 20,/* internal: band subgraph has a cycle (GraphAligner.h:2362-2397); resolved by the general kernel variants, not returned */
 	GA_S_UNSUPPORTED_RAMP = 21, /* internal: ramp redo (GraphAligner.h:2648-2719) taken; resolved by the general kernel variants, not returned */
 	/* call-level errors */
