@@ -14,7 +14,9 @@ are refused.  An addition of this project: `--find-seeds` (with `--seed-k K`, `-
 for `-s`: the seeds come from the library's k-mer index of the graph (binding.Graph.find_seeds).  `--seed-walks N`
 (1..256; 0, the default: k-mers inside nodes only) builds the walk index, which a graph of nodes shorter than k needs.  `--seed-loci`
 groups a read's hits into loci first and gives one seed per locus (binding.Graph.find_seeds(loci=True)), so that a long read is not
-extended twice from the same place.
+extended twice from the same place.  `--seed-coord file|topology` chooses the linear coordinate the hits are ranked and grouped by: the
+order of the graph file (the default) or the coordinate built from the edges (binding.Graph.set_seed_coordinate), which a graph
+file that is not in path order needs.
 
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq -s seeds.gam -a out.gam -t 1 -b 35
     python -m graphaligner_amd.aligner -g graph.gfa -f reads.fastq --find-seeds -a out.gam -t 1 -b 35
@@ -142,6 +144,7 @@ class AlignerParams:
         self.seedMax = 2
         self.seedWalks = 0          # --seed-walks: 0 = the in-node index, 1..256 = the walk index with that max_walks
         self.seedLoci = False       # --seed-loci: one seed per locus
+        self.seedCoord = "file"     # --seed-coord: "file" or "topology"
 
 
 def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr, seed_lib_path=None):
@@ -170,12 +173,16 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
     if find_seeds:
         seeder = graph if seed_lib_path is None else load_graph(params.graphFile, device=device, lib_path=seed_lib_path)
         walks = getattr(params, "seedWalks", 0)
-        st = seeder.build_seed_index(k=params.seedK, max_walks=walks)
+        coord = getattr(params, "seedCoord", "file")
+        st = seeder.build_seed_index(k=params.seedK, max_walks=walks, coordinate=coord)
         line = "seed index: %d entries of %d k-mers (k %d), %.1f MB" % (st["entries"], st["kmers_seen"], st["k"], st["bytes"] / 1e6)
         if walks:
             ws = seeder.seed_index_walk_stats()
             line += ", walks: %d of %d tail starts skipped (more than %d walks)" % (ws["tail_starts_skipped"], ws["tail_starts"], ws["max_walks"])
         out.write(line + "\n")
+        if coord == "topology":
+            cs = seeder.seed_coord_stats()
+            out.write("seed coordinate: topology, %d trees, %d cycles cut, %d + %d rounds\n" % (cs["trees"], cs["cycles_cut"], cs["cycle_rounds"], cs["depth_rounds"]))
         by_locus = getattr(params, "seedLoci", False)
         found = seeder.find_seeds([r.sequence for r in reads], loci=by_locus, max_seeds=params.seedMax)
         seeds_of = {i: s for i, s in enumerate(found.seeds) if s}
@@ -249,7 +256,8 @@ def parse_args(argv, err=sys.stderr):
     """AlignerMain.cpp:18-107"""
     p = AlignerParams()
     initial_full_band = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci"])
+    coord_given = False
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord="])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -281,6 +289,9 @@ def parse_args(argv, err=sys.stderr):
             p.seedWalks = int(a)
         elif o == "--seed-loci":
             p.seedLoci = True
+        elif o == "--seed-coord":
+            p.seedCoord = a
+            coord_given = True
 
     def stop(msg):
         err.write(msg + "\n")
@@ -303,6 +314,8 @@ def parse_args(argv, err=sys.stderr):
         stop("--seed-walks must be 0..256 and goes with --find-seeds")
     if p.seedLoci and not p.findSeeds:
         stop("--seed-loci goes with --find-seeds")
+    if p.seedCoord not in ("file", "topology") or (coord_given and not p.findSeeds):
+        stop("--seed-coord must be file or topology and goes with --find-seeds")
     if initial_full_band:
         stop("-i (alignment without seeds) is not part of the GPU hot path; it asserts in the reference snapshot (GraphAligner.h:1138)")
     if p.auggraphFile != "":

@@ -75,6 +75,14 @@ class GaSeedWalkStats(C.Structure):
                 ("max_walks", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class GaSeedCoordStats(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("trees", C.c_uint32), ("cycles_cut", C.c_uint32), ("cycle_rounds", C.c_uint32), ("depth_rounds", C.c_uint32),
+                ("reserved", C.c_uint32), ("extent_sum", C.c_uint64), ("build_ms", C.c_double)]
+
+
+SEED_COORDINATES = {"file": 0, "topology": 1}
+
+
 class GaSeedSet(C.Structure):
     _fields_ = [("n_reads", C.c_size_t), ("seed_offsets", C.POINTER(C.c_size_t)), ("seeds", C.POINTER(GaSeed)), ("support", C.POINTER(C.c_uint32)),
                 ("n_hits", C.POINTER(C.c_uint32)), ("truncated", C.POINTER(C.c_uint8)), ("kernel_ms", C.c_double)]
@@ -89,7 +97,8 @@ class GaSeedSetLoci(C.Structure):
 
 # the seeding entry points: in the product library and in tests/_build/libga_seed_emul.so, not in the alignment-only emulation
 SEED_EXPORTS = ["ga_seed_params_default", "ga_graph_build_seed_index", "ga_graph_seed_index_stats", "ga_graph_seed_index_copy", "ga_find_seeds",
-                "ga_seed_set_free", "ga_graph_build_seed_index_walks", "ga_graph_seed_index_walk_stats", "ga_find_seeds_loci"]
+                "ga_seed_set_free", "ga_graph_build_seed_index_walks", "ga_graph_seed_index_walk_stats", "ga_find_seeds_loci",
+                "ga_graph_set_seed_coordinate", "ga_graph_seed_coord_stats", "ga_graph_seed_coordinate_copy"]
 
 EXPORTS = ["ga_graph_create", "ga_graph_destroy", "ga_graph_add_node", "ga_graph_add_edge", "ga_graph_add_bigraph_node",
            "ga_graph_add_bigraph_edge", "ga_graph_finalize", "ga_graph_load_gfa", "ga_graph_upload", "ga_graph_node_count", "ga_graph_bp",
@@ -150,6 +159,10 @@ def load(path=None):
         L.ga_find_seeds.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         if hasattr(L, "ga_find_seeds_loci"):                               # (nor has such a build seeds per locus)
             L.ga_find_seeds_loci.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        if hasattr(L, "ga_graph_set_seed_coordinate"):                     # (nor the topology coordinate)
+            L.ga_graph_set_seed_coordinate.argtypes = [C.c_void_p, C.c_int]
+            L.ga_graph_seed_coord_stats.argtypes = [C.c_void_p, C.c_void_p]
+            L.ga_graph_seed_coordinate_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.ga_seed_set_free.argtypes = [C.c_void_p]
         L.ga_seed_set_free.restype = None
     _libs[path] = L
@@ -213,15 +226,43 @@ class Graph:
         if not hasattr(self.L, "ga_find_seeds"):
             raise RuntimeError("this library has no seeding entry points")
 
-    def build_seed_index(self, k=15, sample_shift=2, max_walks=0):
+    def build_seed_index(self, k=15, sample_shift=2, max_walks=0, coordinate="file"):
         """k-mer index of this graph in HBM (replaces an earlier one); returns its statistics.  max_walks 0: k-mers inside nodes;
-        1..256: the walk index for graphs of short nodes (k-mers across edges, starts with more walks than that left out)"""
+        1..256: the walk index for graphs of short nodes (k-mers across edges, starts with more walks than that left out).
+        coordinate: "file" (the order the nodes were added in) or "topology" (built from the edges: set_seed_coordinate)"""
         self._need_seeding()
+        if coordinate not in SEED_COORDINATES:
+            raise ValueError("build_seed_index: coordinate must be one of %s" % ", ".join(sorted(SEED_COORDINATES)))
         if max_walks:
             _check(self.L, self.L.ga_graph_build_seed_index_walks(self.h, int(k), int(sample_shift), int(max_walks)), "ga_graph_build_seed_index_walks")
         else:
             _check(self.L, self.L.ga_graph_build_seed_index(self.h, int(k), int(sample_shift)), "ga_graph_build_seed_index")
+        if coordinate != "file":
+            self.set_seed_coordinate(coordinate)
         return self.seed_index_stats()
+
+    def set_seed_coordinate(self, kind):
+        """replaces the linear coordinate of the current index: "file" or "topology" (or GA_SEED_COORD_*: 0, 1); returns the
+        statistics of ga_seed_coord_stats_t as a dict.  Every build_seed_index starts in file order again."""
+        self._need_seeding()
+        if not hasattr(self.L, "ga_graph_set_seed_coordinate"):
+            raise RuntimeError("this library has no ga_graph_set_seed_coordinate")
+        _check(self.L, self.L.ga_graph_set_seed_coordinate(self.h, int(SEED_COORDINATES.get(kind, kind))), "ga_graph_set_seed_coordinate")
+        return self.seed_coord_stats()
+
+    def seed_coord_stats(self):
+        self._need_seeding()
+        st = GaSeedCoordStats()
+        _check(self.L, self.L.ga_graph_seed_coord_stats(self.h, C.byref(st)), "ga_graph_seed_coord_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def seed_coordinate(self):
+        """lin of every node by node index (numpy int64; the two dummy nodes at both ends included): for tests and tools"""
+        self._need_seeding()
+        n = int(self.L.ga_graph_node_count(self.h))
+        lin = np.zeros(max(n, 1), dtype=np.int64)
+        _check(self.L, self.L.ga_graph_seed_coordinate_copy(self.h, lin.ctypes.data_as(C.c_void_p), n), "ga_graph_seed_coordinate_copy")
+        return lin[:n]
 
     def seed_index_walk_stats(self):
         """tail starts, skipped ones, walk k-mers and dropped duplicates of a walk index (an error for an in-node index)"""

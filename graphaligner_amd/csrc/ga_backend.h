@@ -92,6 +92,8 @@ struct GaSeedOut
 	std::vector<uint32_t> locus_hits, locus_first_p, locus_last_p, n_loci;
 	double kernel_ms = 0;
 };
+// the coordinate of the current index (include/graphaligner_amd.h: ga_seed_coord_stats_t); kind 0 = file order, where the rest is 0
+struct GaSeedCoordInfo { int kind = 0; uint32_t trees = 0, cycles_cut = 0, cycle_rounds = 0, depth_rounds = 0; uint64_t extent_sum = 0; double build_ms = 0; };
 class GaSeedEngine
 {
 public:
@@ -108,6 +110,12 @@ public:
 	virtual int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) = 0;
 	// the same with one seed per locus (ga_find_seeds_loci); a back end without it refuses (100 = GA_E_INVALID)
 	virtual int findLoci(const char* const*, const size_t*, size_t, const GaSeedParams&, GaSeedOut&) { return 100; }
+	// replaces the coordinate of the current index: 0 file order (the array build() was given), 1 topology (ga_seed.h); a back end
+	// without the topology pass keeps the file order it has and refuses the rest (100 = GA_E_INVALID)
+	virtual int setCoordinate(int kind, GaSeedCoordInfo& out) { if (kind != 0 || !built()) return 100; out = GaSeedCoordInfo(); return 0; }
+	virtual GaSeedCoordInfo coordInfo() const { return GaSeedCoordInfo(); }
+	// lin of the first min(n_nodes, capacity) nodes as the index holds it now
+	virtual int copyLin(int64_t*, size_t) const { return 100; }
 };
 
 class GaBackendGraph

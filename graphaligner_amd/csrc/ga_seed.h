@@ -22,9 +22,11 @@ namespace gas {
 
 #ifdef GA_EMULATE
 #define GAS_FN inline
+#define GAS_HOST_FN inline
 #define GAS_LANES(l) for (int l = 0; l < 64; l++)
 #else
 #define GAS_FN __device__ __forceinline__
+#define GAS_HOST_FN __host__ __device__ inline                 // what the engine's host code calls too
 #define GAS_LANES(l) if (const int l = (int)threadIdx.x; true)
 #endif
 
@@ -687,6 +689,134 @@ GAS_FN void seed_wave(const SeedLaunch& L, SeedLds& lds, uint32_t slot, uint32_t
 GAS_FN void seed_wave_loci(const SeedLaunch& L, SeedLdsLoci& lds, uint32_t slot, uint32_t slots)
 {
 	for (uint32_t at = slot; at < L.n_reads; at += slots) seed_read_loci(L, lds, slot, L.order[at]);
+}
+
+// ---- topology coordinate ---------------------------------------------------------------------------------------------------------
+// The linear coordinate from the graph's edges instead of the order of the file (include/graphaligner_amd.h, "topology coordinate",
+// has the rule; DESIGN.md section 10b argues it): every node hangs under the first usable entry of its in-list, the cycles of that
+// relation are cut at their smallest node index, lin = the tree's base + the summed length of the node's ancestors.  One lane per
+// node.  Every function below is one node's part of one launch: it reads the launch's input buffers, writes the node's own entry of
+// the output buffer (coord_mark and coord_extent: an entry of another node, by a store of the constant 1 and by an integer max, so
+// the order of the lanes does not show), and returns what the launch counts or ors together.  The loops over rounds are the host's.
+// Work buffers, freed when the call ends, 68 bytes per node: two state buffers of 16 bytes (the cycle pass uses 8 of each), parent
+// and its length 4 + 4, marks 4, extents 8, the scan's input and output 8 + 8.
+constexpr uint32_t kCoordRoot = 0xffffffffu;       // "no parent": what the cycle pass calls the ancestor of a walk that has left its tree
+constexpr int64_t kTreeGap = 1 << 20;              // GA_SEED_TREE_GAP
+struct alignas(8) CoordCyc { uint32_t anc, low; };                  // ancestor 2^r steps up, smallest index among the 2^r nodes before it
+struct alignas(16) CoordDepth { int64_t dist; uint32_t anc, reserved; };   // ancestor min(2^r, all) steps up (a root: itself), columns from its first to the node's first
+
+GAS_FN bool coord_dummy(const GaDevGraph& g, uint32_t v) { return v == 0 || v + 1 >= g.n_nodes; }
+GAS_HOST_FN uint32_t coord_rounds(uint32_t nNodes) { uint32_t r = 0; while ((1ull << r) < nNodes) r++; return r; }   // smallest R with 2^R >= n_nodes
+
+// the parent: the first entry of the in-list that is neither the node itself nor a dummy node.  The node's record holds the first
+// four entries and their lengths; a longer list is read itself
+GAS_FN void coord_parent(const GaDevGraph& g, uint32_t v, uint32_t* par, uint32_t* parLen)
+{
+	uint32_t p = kCoordRoot, pl = 0;
+	if (!coord_dummy(g, v))
+	{
+		const uint32_t* r = g.node_rec + (uint64_t)v * GA_NODE_REC_WORDS;
+		const uint32_t inDeg = r[3] & 0xffffu;
+		bool found = false;
+		if (inDeg <= 4)
+		{
+#pragma unroll
+			for (uint32_t k = 0; k < 4; k++)
+			{
+				const uint32_t u = r[8 + k], ul = r[12 + k];
+				if (k < inDeg && !found && u != v && !coord_dummy(g, u)) { p = u; pl = ul; found = true; }
+			}
+		}
+		else
+		{
+			const uint32_t end = g.in_off[v + 1];
+			for (uint32_t e = g.in_off[v]; e < end && !found; e++)
+			{
+				const uint32_t u = g.in_nbr[e];
+				if (u != v && !coord_dummy(g, u)) { p = u; pl = (uint32_t)(g.node_start[u + 1] - g.node_start[u]); found = true; }
+			}
+		}
+	}
+	par[v] = p; parLen[v] = pl;
+}
+// cycle pass.  After r rounds: anc = the node r' = 2^r parent steps up (kCoordRoot once the walk has passed a root), low = the smallest
+// index among the node and the walk's nodes before anc.  Returns whether the node's walk is still inside the graph.
+GAS_FN bool coord_cyc_init(const uint32_t* par, uint32_t v, CoordCyc* o)
+{
+	const uint32_t p = par[v];
+	o[v] = CoordCyc{p, v};
+	return p != kCoordRoot;
+}
+GAS_FN bool coord_cyc_round(const CoordCyc* a, CoordCyc* o, uint32_t v)
+{
+	CoordCyc s = a[v];
+	if (s.anc != kCoordRoot)
+	{
+		const CoordCyc t = a[s.anc];
+		s.anc = t.anc; s.low = t.low < s.low ? t.low : s.low;
+	}
+	o[v] = s;
+	return s.anc != kCoordRoot;
+}
+// after R rounds with 2^R >= n_nodes a walk that is still inside the graph never ends: its node 2^R steps up lies on a cycle, and
+// from the nodes of a cycle those are all its nodes (2^R steps turn the cycle onto itself).  For a node ON a cycle the 2^R nodes
+// of its walk are the cycle's, so there `low` is the cycle's smallest index; for a node that leads into one, `low` may be its own
+GAS_FN void coord_mark(const CoordCyc* a, uint32_t* mark, uint32_t v)
+{
+	const uint32_t t = a[v].anc;
+	if (t != kCoordRoot) mark[t] = 1;
+}
+GAS_FN bool coord_cut(const CoordCyc* a, const uint32_t* mark, uint32_t* par, uint32_t v)
+{
+	const bool cut = mark[v] != 0 && a[v].low == v;
+	if (cut) par[v] = kCoordRoot;
+	return cut;
+}
+// depth pass over the forest that is left: a root is its own ancestor at distance 0, so a walk stays at its root.  Returns whether
+// the node's ancestor changed
+GAS_FN bool coord_depth_init(const uint32_t* par, const uint32_t* parLen, uint32_t v, CoordDepth* o)
+{
+	const uint32_t p = par[v];
+	o[v] = p == kCoordRoot ? CoordDepth{0, v, 0} : CoordDepth{(int64_t)parLen[v], p, 0};
+	return p != kCoordRoot;
+}
+GAS_FN bool coord_depth_round(const CoordDepth* a, CoordDepth* o, uint32_t v)
+{
+	const CoordDepth s = a[v], t = a[s.anc];
+	o[v] = CoordDepth{s.dist + t.dist, t.anc, 0};                         // (s.anc a root: t = {0, s.anc})
+	return t.anc != s.anc;
+}
+// the tree's extent, at its root's entry (zeroed before the launch, then touched by acc_* alone until the next launch has read it).
+// coord_extent_of: what one node gives, its root and depth + length (false: a dummy node); coord_extent: the integer max there.  On
+// gfx950 the launch first takes the max over the lanes of a wave that share a root (ga_seed_dev.h) and sends one value per wave and
+// root, so that the nodes of a long chain do not queue at one address; the maximum is the same
+GAS_FN bool coord_extent_of(const GaDevGraph& g, const CoordDepth* a, uint32_t v, uint32_t& root, uint64_t& end)
+{
+	if (coord_dummy(g, v)) return false;
+	const CoordDepth s = a[v];
+	root = s.anc;
+	end = (uint64_t)s.dist + (g.node_start[v + 1] - g.node_start[v]);
+	return true;
+}
+GAS_FN void coord_extent(const GaDevGraph& g, const CoordDepth* a, uint64_t* ext, uint32_t v)
+{
+	uint32_t root = 0;
+	uint64_t end = 0;
+	if (coord_extent_of(g, a, v, root, end)) acc_max(ext + root, end);
+}
+// what the scan sums: extent + gap at a root (the exclusive scan in node index order then gives every root its tree's base)
+GAS_FN bool coord_contrib(const GaDevGraph& g, const CoordDepth* a, const uint64_t* ext, uint64_t* contrib, uint32_t v)
+{
+	const bool root = !coord_dummy(g, v) && a[v].anc == v;
+	contrib[v] = root ? acc_get(ext + v) + (uint64_t)kTreeGap : 0;
+	return root;
+}
+// 2 * lin + the strand flag the entry holds already (digraph id & 1 in either coordinate); the dummy nodes stay at 0
+GAS_FN void coord_write(const GaDevGraph& g, const CoordDepth* a, const uint64_t* base, int64_t* linx, uint32_t v)
+{
+	if (coord_dummy(g, v)) { linx[v] = 0; return; }
+	const CoordDepth s = a[v];
+	linx[v] = ((int64_t)base[s.anc] + s.dist) * 2 + (linx[v] & 1);
 }
 
 }  // namespace gas

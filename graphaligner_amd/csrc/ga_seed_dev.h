@@ -77,6 +77,84 @@ __global__ void __launch_bounds__(256) ga_seed_compact_kernel(const uint64_t* ke
 	const uint32_t at = pos[i];
 	if (pos[i + 1] != at) { outKeys[at] = keys[i]; outVals[at] = vals[i]; }
 }
+// the topology coordinate (ga_seed.h): one lane per node, one launch per step; a launch ors "still moving" into a word of its own, which
+// the host reads before it decides on the next launch, and the two counting launches add the wave's count to a counter
+__device__ __forceinline__ void coord_flag(bool moving, uint32_t* flag)
+{
+	if (__ballot(moving) != 0 && (threadIdx.x & 63) == 0) *flag = 1;       // (every wave that writes writes 1)
+}
+__device__ __forceinline__ void coord_count(bool one, uint32_t* counter)
+{
+	const uint64_t m = __ballot(one);
+	if (m != 0 && (threadIdx.x & 63) == 0) atomicAdd(counter, (uint32_t)__builtin_popcountll(m));
+}
+__global__ void __launch_bounds__(256) ga_coord_parent_kernel(GaDevGraph g, uint32_t* par, uint32_t* parLen, gas::CoordCyc* cyc, uint32_t* flag)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	bool mv = false;
+	if (v < g.n_nodes) { gas::coord_parent(g, v, par, parLen); mv = gas::coord_cyc_init(par, v, cyc); }
+	coord_flag(mv, flag);
+}
+__global__ void __launch_bounds__(256) ga_coord_cyc_round_kernel(uint32_t n, const gas::CoordCyc* a, gas::CoordCyc* o, uint32_t* flag)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	coord_flag(v < n && gas::coord_cyc_round(a, o, v), flag);
+}
+__global__ void __launch_bounds__(256) ga_coord_mark_kernel(uint32_t n, const gas::CoordCyc* a, uint32_t* mark)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	if (v < n) gas::coord_mark(a, mark, v);
+}
+__global__ void __launch_bounds__(256) ga_coord_cut_kernel(uint32_t n, const gas::CoordCyc* a, const uint32_t* mark, uint32_t* par, uint32_t* cuts)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	coord_count(v < n && gas::coord_cut(a, mark, par, v), cuts);
+}
+__global__ void __launch_bounds__(256) ga_coord_depth_init_kernel(uint32_t n, const uint32_t* par, const uint32_t* parLen, gas::CoordDepth* o, uint32_t* flag)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	coord_flag(v < n && gas::coord_depth_init(par, parLen, v, o), flag);
+}
+__global__ void __launch_bounds__(256) ga_coord_depth_round_kernel(uint32_t n, const gas::CoordDepth* a, gas::CoordDepth* o, uint32_t* flag)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	coord_flag(v < n && gas::coord_depth_round(a, o, v), flag);
+}
+// one max per wave and root: the lanes that share the root of the first lane still left take their max by butterfly, that lane sends
+// it, and they leave; a counted loop whose exit is the wave's own ballot (one pass on a chain, at most 64 when every lane has another root)
+__global__ void __launch_bounds__(256) ga_coord_extent_kernel(GaDevGraph g, const gas::CoordDepth* a, uint64_t* ext)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	const int lane = (int)(threadIdx.x & 63);
+	uint32_t root = 0;
+	uint64_t end = 0;
+	bool have = v < g.n_nodes && gas::coord_extent_of(g, a, v, root, end);
+	uint64_t left = __ballot(have);
+	for (int pass = 0; pass < 64 && left != 0; pass++)
+	{
+		const int first = __builtin_ctzll(left);
+		const uint32_t r = (uint32_t)__shfl((int)root, first, 64);
+		const bool mine = have && root == r;
+		unsigned long long m = mine ? end : 0ull;
+		for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(m, d, 64); m = o > m ? o : m; }
+		if (lane == first) gas::acc_max(ext + r, (uint64_t)m);
+		have = have && !mine;
+		left = __ballot(have);
+	}
+}
+__global__ void __launch_bounds__(256) ga_coord_contrib_kernel(GaDevGraph g, const gas::CoordDepth* a, const uint64_t* ext, uint64_t* contrib, uint32_t* trees)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	bool root = false;
+	if (v < g.n_nodes) root = gas::coord_contrib(g, a, ext, contrib, v);
+	else if (v == g.n_nodes) contrib[v] = 0;                              // (the scan's last element = the sum over the trees)
+	coord_count(root, trees);
+}
+__global__ void __launch_bounds__(256) ga_coord_write_kernel(GaDevGraph g, const gas::CoordDepth* a, const uint64_t* base, int64_t* linx)
+{
+	const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+	if (v < g.n_nodes) gas::coord_write(g, a, base, linx, v);
+}
 // the hot path: one wave per read at a time
 __global__ void __launch_bounds__(64) ga_seed_find_kernel(gas::SeedLaunch L)
 {
@@ -106,6 +184,8 @@ struct DevSeedEngine : GaSeedEngine
 	GaSeedIndexInfo inf;
 	GaSeedWalkInfo winf;
 	bool have = false;
+	std::vector<int64_t> linxFile;             // the file-order coordinate build() was given: what kind 0 puts back
+	GaSeedCoordInfo cinf;
 	void* dKeys = nullptr; void* dVals = nullptr; void* dDir = nullptr; void* dLinx = nullptr;
 	// buffers of find(), kept between calls
 	void* work = nullptr; size_t workBytes = 0;
@@ -251,7 +331,111 @@ struct DevSeedEngine : GaSeedEngine
 		inf.bytes = (uint64_t)n * 16 + ((uint64_t)buckets + 1) * 4 + (uint64_t)linx.size() * 8;
 		inf.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		winf = w;
+		linxFile = linx;
+		cinf = GaSeedCoordInfo();
 		have = true;
+		return 0;
+	}
+
+	GaSeedCoordInfo coordInfo() const override { return cinf; }
+	int copyLin(int64_t* lin, size_t capacity) const override
+	{
+		if (!have) return 100;
+		const size_t n = std::min<size_t>(capacity, g.n_nodes);
+		if (n == 0) return 0;
+		GAS_HIP_OK(hipSetDevice(device));
+		GAS_HIP_OK(hipMemcpy(lin, dLinx, n * 8, hipMemcpyDeviceToHost));
+		for (size_t i = 0; i < n; i++) lin[i] >>= 1;
+		return 0;
+	}
+
+	// kind 1: the passes of ga_seed.h ("topology coordinate"), the last of which writes dLinx; the index itself is not touched
+	int setCoordinate(int kind, GaSeedCoordInfo& out) override
+	{
+		std::lock_guard<std::mutex> guard(lock);
+		if (!have || (kind != 0 && kind != 1)) return 100;
+		GAS_HIP_OK(hipSetDevice(device));
+		if (kind == 0)
+		{
+			GAS_HIP_OK(hipMemcpy(dLinx, linxFile.data(), linxFile.size() * 8, hipMemcpyHostToDevice));
+			cinf = GaSeedCoordInfo();
+			out = cinf;
+			return 0;
+		}
+		const auto t0 = std::chrono::steady_clock::now();
+		const uint32_t n = g.n_nodes, blocks = (n + 255) / 256, blocks1 = (n + 1 + 255) / 256, R = gas::coord_rounds(n);
+		// control words: "still moving" of the cycle pass' start and of each of its <= R rounds, of the depth pass' start and of each of
+		// its <= R + 1 rounds, then the two counters
+		const uint32_t fCyc = 0, fDepth = R + 1, cCuts = 2 * R + 3, cTrees = cCuts + 1, nCtl = cTrees + 1;
+		void* stA = nullptr; void* stB = nullptr; uint32_t* par = nullptr; uint32_t* parLen = nullptr; uint32_t* mark = nullptr;
+		uint64_t* ext = nullptr; uint64_t* contrib = nullptr; uint64_t* base = nullptr; uint32_t* ctl = nullptr; void* tmp = nullptr;
+		auto cleanup = [&]() { for (void* p : {stA, stB, (void*)par, (void*)parLen, (void*)mark, (void*)ext, (void*)contrib, (void*)base, (void*)ctl, tmp}) if (p) hipFree(p); };
+#define GAS_TRY(call) do { if ((call) != hipSuccess) { fprintf(stderr, "graphaligner_amd: %s failed\n", #call); cleanup(); return 102; } } while (0)
+		GAS_TRY(hipMalloc(&stA, (size_t)n * 16));
+		GAS_TRY(hipMalloc(&stB, (size_t)n * 16));
+		GAS_TRY(hipMalloc((void**)&par, (size_t)n * 4));
+		GAS_TRY(hipMalloc((void**)&parLen, (size_t)n * 4));
+		GAS_TRY(hipMalloc((void**)&mark, (size_t)n * 4));
+		GAS_TRY(hipMalloc((void**)&ext, (size_t)n * 8));
+		GAS_TRY(hipMalloc((void**)&contrib, ((size_t)n + 1) * 8));
+		GAS_TRY(hipMalloc((void**)&base, ((size_t)n + 1) * 8));
+		GAS_TRY(hipMalloc((void**)&ctl, (size_t)nCtl * 4));
+		GAS_TRY(hipMemsetAsync(ctl, 0, (size_t)nCtl * 4, 0));
+		GAS_TRY(hipMemsetAsync(mark, 0, (size_t)n * 4, 0));
+		GAS_TRY(hipMemsetAsync(ext, 0, (size_t)n * 8, 0));
+		auto moving = [&](uint32_t word, bool& mv) { uint32_t w = 0; const hipError_t e = hipMemcpy(&w, ctl + word, 4, hipMemcpyDeviceToHost); mv = w != 0; return e; };
+		GaSeedCoordInfo c;
+		c.kind = 1;
+		// parents, and the cycle pass over them
+		gas::CoordCyc* ca = (gas::CoordCyc*)stA; gas::CoordCyc* co = (gas::CoordCyc*)stB;
+		hipLaunchKernelGGL(ga_coord_parent_kernel, dim3(blocks), dim3(256), 0, 0, g, par, parLen, ca, ctl + fCyc);
+		bool mv = false;
+		GAS_TRY(moving(fCyc, mv));
+		while (mv && c.cycle_rounds < R)
+		{
+			hipLaunchKernelGGL(ga_coord_cyc_round_kernel, dim3(blocks), dim3(256), 0, 0, n, (const gas::CoordCyc*)ca, co, ctl + fCyc + 1 + c.cycle_rounds);
+			GAS_TRY(moving(fCyc + 1 + c.cycle_rounds, mv));
+			c.cycle_rounds++;
+			std::swap(ca, co);
+		}
+		if (mv)
+		{
+			// walks that never end: mark the cycles' nodes, cut every cycle at its smallest index
+			hipLaunchKernelGGL(ga_coord_mark_kernel, dim3(blocks), dim3(256), 0, 0, n, (const gas::CoordCyc*)ca, mark);
+			hipLaunchKernelGGL(ga_coord_cut_kernel, dim3(blocks), dim3(256), 0, 0, n, (const gas::CoordCyc*)ca, (const uint32_t*)mark, par, ctl + cCuts);
+		}
+		// depths in the forest
+		gas::CoordDepth* da = (gas::CoordDepth*)stA; gas::CoordDepth* dd = (gas::CoordDepth*)stB;
+		hipLaunchKernelGGL(ga_coord_depth_init_kernel, dim3(blocks), dim3(256), 0, 0, n, (const uint32_t*)par, (const uint32_t*)parLen, da, ctl + fDepth);
+		GAS_TRY(moving(fDepth, mv));
+		while (mv && c.depth_rounds < R + 1)
+		{
+			hipLaunchKernelGGL(ga_coord_depth_round_kernel, dim3(blocks), dim3(256), 0, 0, n, (const gas::CoordDepth*)da, dd, ctl + fDepth + 1 + c.depth_rounds);
+			GAS_TRY(moving(fDepth + 1 + c.depth_rounds, mv));
+			c.depth_rounds++;
+			std::swap(da, dd);
+		}
+		if (mv) { cleanup(); return 102; }                                  // (never: a forest's walks are at their roots after R rounds)
+		// extents at the roots, bases by a scan in node index order, the write
+		hipLaunchKernelGGL(ga_coord_extent_kernel, dim3(blocks), dim3(256), 0, 0, g, (const gas::CoordDepth*)da, ext);
+		hipLaunchKernelGGL(ga_coord_contrib_kernel, dim3(blocks1), dim3(256), 0, 0, g, (const gas::CoordDepth*)da, (const uint64_t*)ext, contrib, ctl + cTrees);
+		size_t tmpBytes = 0;
+		GAS_TRY(rocprim::exclusive_scan(nullptr, tmpBytes, contrib, base, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>()));
+		GAS_TRY(hipMalloc(&tmp, std::max<size_t>(tmpBytes, 16)));
+		GAS_TRY(rocprim::exclusive_scan(tmp, tmpBytes, contrib, base, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>()));
+		hipLaunchKernelGGL(ga_coord_write_kernel, dim3(blocks), dim3(256), 0, 0, g, (const gas::CoordDepth*)da, (const uint64_t*)base, (int64_t*)dLinx);
+		uint64_t total = 0;
+		uint32_t counts[2] = {0, 0};
+		GAS_TRY(hipMemcpy(&total, base + n, 8, hipMemcpyDeviceToHost));
+		GAS_TRY(hipMemcpy(counts, ctl + cCuts, 8, hipMemcpyDeviceToHost));
+		GAS_TRY(hipDeviceSynchronize());
+#undef GAS_TRY
+		cleanup();
+		c.cycles_cut = counts[0]; c.trees = counts[1];
+		c.extent_sum = total - (uint64_t)c.trees * (uint64_t)gas::kTreeGap;
+		c.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		cinf = c;
+		out = c;
 		return 0;
 	}
 

@@ -108,6 +108,37 @@ int ga_graph_seed_index_stats(const ga_graph_t* g, ga_seed_index_stats_t* out)
 	return GA_S_OK;
 }
 
+int ga_graph_set_seed_coordinate(ga_graph_t* g, int kind)
+{
+	GaGraphView v;
+	GaSeedEngine* e = nullptr;
+	if (int s = engineOf(g, v, &e)) return s;
+	if (!e->built() || (kind != GA_SEED_COORD_FILE_ORDER && kind != GA_SEED_COORD_TOPOLOGY)) return GA_E_INVALID;
+	GaSeedCoordInfo c;
+	return e->setCoordinate(kind, c);
+}
+
+int ga_graph_seed_coord_stats(const ga_graph_t* g, ga_seed_coord_stats_t* out)
+{
+	GaGraphView v;
+	GaSeedEngine* e = nullptr;
+	if (int s = engineOf(g, v, &e)) return s;
+	if (!out || !e->built()) return GA_E_INVALID;
+	const GaSeedCoordInfo c = e->coordInfo();
+	out->kind = c.kind; out->trees = c.trees; out->cycles_cut = c.cycles_cut; out->cycle_rounds = c.cycle_rounds; out->depth_rounds = c.depth_rounds;
+	out->reserved = 0; out->extent_sum = c.extent_sum; out->build_ms = c.build_ms;
+	return GA_S_OK;
+}
+
+int ga_graph_seed_coordinate_copy(const ga_graph_t* g, int64_t* lin, size_t capacity)
+{
+	GaGraphView v;
+	GaSeedEngine* e = nullptr;
+	if (int s = engineOf(g, v, &e)) return s;
+	if (!e->built() || (capacity && !lin)) return GA_E_INVALID;
+	return e->copyLin(lin, capacity);
+}
+
 int ga_graph_seed_index_copy(const ga_graph_t* g, uint64_t* keys, uint32_t* node_indices, uint32_t* offsets, size_t capacity)
 {
 	GaGraphView v;

@@ -222,7 +222,8 @@ int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out);
  * give one entry.  Order, lookup, hits, support, candidates and choice are those above; diag uses the start's node and o.  Both strands
  * are nodes, so reverse-complement k-mers come from the reverse nodes' own walks.  The index does not depend on where a sequence is cut
  * into nodes as long as no tail start is skipped; it grows with the variants per k bases (2^v walks over v SNPs).
- * LIMITS: the linear coordinate follows the order in which nodes were added, not topology: it ranks, it never decides an alignment
+ * LIMITS: the linear coordinate follows the order in which nodes were added, not topology (unless the topology coordinate below is
+ * asked for): it ranks, it never decides an alignment
  * (a wrongly ranked seed costs a wasted extension); a read shorter than 386 bp gets no seed (either direction would be under the 193 bp the
  * reference's engine asserts on, GraphAligner.h:906).
  * ONE SEED PER LOCUS (ga_find_seeds_loci).  Along a long read the diagonal drifts (the read's indels, the file-order coordinate stepping
@@ -238,6 +239,25 @@ int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out);
  * taken locus is returned, in that order.  Loci are ranked by size because the best-supported single hit can lie in a partial copy of a
  * repeat: with max_seeds = 1 ga_find_seeds_loci can therefore name a different seed than ga_find_seeds does.  A structural variant longer
  * than diag_tol still splits a locus in two (the coordinate is file order), which costs one extension.
+ * TOPOLOGY COORDINATE (ga_graph_set_seed_coordinate with GA_SEED_COORD_TOPOLOGY).  The file-order coordinate is only as good as the
+ * file's order: with unsorted ids, alleles appended after the backbone or contigs interleaved, two neighbouring nodes of a walk have
+ * unrelated lin and support falls to the hits inside one node.  The topology coordinate is built on the device from the edges.  Nodes
+ * are digraph nodes, both strands, by node index; the two dummy nodes take no part and get lin = 0; len(v) is v's length in columns.
+ * PARENT: parent(v) is the first entry u of v's in-neighbour list, in its stored order, with u != v and u not a dummy node; a node
+ * without one is a root.  CYCLES: on each cycle of the parent relation the node with the smallest node index becomes a root (its
+ * parent link is dropped); what remains is a forest.  DEPTH: depth(root) = 0, depth(v) = depth(parent(v)) + len(parent(v)); tree(v)
+ * is v's root.  EXTENT of a tree: the maximum of depth(v) + len(v) over its nodes.  BASE: trees are ordered by their root's node
+ * index; the first has base 0, each next one base(previous) + extent(previous) + GA_SEED_TREE_GAP.  lin(v) = base(tree(v)) + depth(v),
+ * a 64-bit integer, and the strand flag stays digraph id & 1.  Both strands are nodes with their own in-lists, so the reverse strand
+ * gets trees of its own and no mirrored sign.  Everything else of the rule (diag, support, link, candidates, choice) is unchanged; only
+ * the 8 bytes per node that hold lin change.  The gap keeps hits of different trees from ever being linked or counted as support; this
+ * holds while window + diag_tol < GA_SEED_TREE_GAP = 2^20 (two hits within window of each other whose nodes lie in different trees
+ * have diagonals at least 2^20 - window apart).
+ * LIMITS of the topology coordinate: where a node has in-neighbours of different depth the coordinate follows the first one, and a
+ * read through the other allele sees a step of the length difference, as any one-dimensional coordinate must; the cut of a cycle
+ * splits the locus of a read that crosses it; a tree that spans an inversion edge has nodes of both strand flags, and support still
+ * counts one flag at a time.  While the coordinate is built the device holds 68 bytes per node of work buffers (freed when the call
+ * ends) and the scan's temporary storage; every pass takes at most ceil(log2(nodes)) + 1 rounds, one launch each.
  * Memory kept with the graph (freed by ga_graph_destroy or a new ga_graph_upload): the index (16 bytes per entry, 4 per directory bucket, 8
  * per node) and, from the first ga_find_seeds on, the last batch's device buffers and the waves' hit buffers (16 waves per CU x max_hits
  * x 20 bytes: 335 MB at the defaults on 256 CUs).  ga_find_seeds_loci runs 24 waves per CU and keeps 28 bytes more per hit (labels, locus
@@ -285,6 +305,28 @@ int ga_graph_seed_index_walk_stats(const ga_graph_t* g, ga_seed_walk_stats_t* ou
 /* the index in its order, for tests and tools: the first min(entries, capacity) entries; node INDICES (0 = the dummy start node; bigraph
  * node number i of a graph built with ga_graph_add_bigraph_node alone is 1 + 2i forward, 2 + 2i reverse) */
 int ga_graph_seed_index_copy(const ga_graph_t* g, uint64_t* keys, uint32_t* node_indices, uint32_t* offsets, size_t capacity);
+
+/* the coordinate of the current index (see TOPOLOGY COORDINATE above).  Every index build starts in file order.  Called after an index
+ * build (GA_E_INVALID without an index or for an unknown kind); it waits for a running ga_find_seeds of the graph and replaces the
+ * coordinate in place, the index entries stay.  GA_SEED_COORD_FILE_ORDER puts back exactly the array the build made. */
+#define GA_SEED_COORD_FILE_ORDER 0
+#define GA_SEED_COORD_TOPOLOGY 1
+#define GA_SEED_TREE_GAP (1 << 20)
+int ga_graph_set_seed_coordinate(ga_graph_t* g, int kind);
+typedef struct ga_seed_coord_stats {
+	int32_t kind;            /* GA_SEED_COORD_*; file order: everything below is 0 */
+	uint32_t trees;          /* roots of the forest, the cut ones included */
+	uint32_t cycles_cut;     /* cycles of the parent relation = roots made by a cut */
+	uint32_t cycle_rounds;   /* doubling rounds of the cycle pass: ceil(log2(nodes, dummies included)) when there is a cycle, else the
+	                            smallest r with 2^r > parent steps of the longest chain */
+	uint32_t depth_rounds;   /* doubling rounds of the depth pass: 0 without an edge, else 1 + the smallest r with 2^r >= those steps */
+	uint32_t reserved;
+	uint64_t extent_sum;     /* summed extents of the trees: the last tree's end = extent_sum + (trees - 1) * GA_SEED_TREE_GAP */
+	double build_ms;         /* wall time of the call's device work */
+} ga_seed_coord_stats_t;
+int ga_graph_seed_coord_stats(const ga_graph_t* g, ga_seed_coord_stats_t* out);
+/* lin of the first min(nodes, capacity) nodes by node index (dummy nodes included), as the index holds it now: for tests and tools */
+int ga_graph_seed_coordinate_copy(const ga_graph_t* g, int64_t* lin, size_t capacity);
 
 typedef struct ga_seed_set {
 	size_t n_reads;

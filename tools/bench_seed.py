@@ -19,6 +19,12 @@ time); everything else in the row is then the walk index's, with its walk statis
 alternating: "loci" holds the grouped kernel's time, its seeds, the jobs and the aligner's kernel_ms from them, its ratio to the
 aligner's kernel_ms from true seeds, and the two sums seeding kernel + aligner kernels, grouped and ungrouped, with the saving and the
 min-max spreads it has to exceed.
+
+--coord topology: the topology coordinate (ga_graph_set_seed_coordinate) measured beside the file-order one on the same batch and
+index, the coordinate switched before every timed call so that the two alternate call by call: "coord" holds the coordinate's build
+time next to the index build's, its rounds, and under either coordinate the ga_find_seeds_loci kernel time, seeds, jobs and the
+aligner's kernel_ms from those seeds.  --shuffle-nodes: the graph's nodes in a random order (random.Random(1).shuffle), edges as they
+are: the file that is not in path order.
 """
 import argparse
 import json
@@ -43,6 +49,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--align-runs", type=int, default=5)
     ap.add_argument("--loci", action="store_true", help="also measure ga_find_seeds_loci (one seed per locus)")
+    ap.add_argument("--coord", choices=["file", "topology"], default="file", help="topology: also measure the topology coordinate")
+    ap.add_argument("--shuffle-nodes", action="store_true", help="node list in a random order")
     args = ap.parse_args()
     if args.node_len < 8 or not 0 <= args.max_walks <= 256:
         raise SystemExit("bench_seed.py: --node-len must be 8 or more and --max-walks 0..256")
@@ -63,6 +71,9 @@ def main():
         g = synth.bubble_graph(args.genome, node_len=args.node_len, seed=44)
     reads, seeds = synth.simulate_reads(g, args.reads, args.read_len, sub=0.04, ins=0.04, dele=0.04, seed=43)
     gen_s = time.time() - t0
+    if args.shuffle_nodes:
+        import random
+        random.Random(1).shuffle(g.nodes)                       # (after the reads: they do not depend on the order)
     G = binding.Graph(gfa=g.gfa())
 
     grouped = {}
@@ -159,6 +170,31 @@ def main():
                                         "spread_grouped": round(float(lms.max() - lms.min()) + spreads[2], 3),
                                         "note": "medians; a spread is max - min of the seeding calls plus max - min of the aligner runs"},
         }
+    if args.coord == "topology":
+        G.set_seed_coordinate("topology")                       # (the first call of a process also loads the kernels)
+        cs = G.set_seed_coordinate("topology")
+        per = {"file": {"ms": [], "found": None}, "topology": {"ms": [], "found": None}}
+        for i in range(args.warmup + args.calls):
+            for kind in ("file", "topology"):
+                G.set_seed_coordinate(kind)
+                f = G.find_seeds(reads, loci=True)
+                if i >= args.warmup:
+                    per[kind]["ms"].append(f.kernel_ms)
+                    per[kind]["found"] = f
+        G.set_seed_coordinate("file")
+        row["coord"] = {"shuffled_nodes": bool(args.shuffle_nodes), "build_ms": round(cs["build_ms"], 3), "index_build_ms": round(st["build_ms"], 2),
+                        "trees": cs["trees"], "cycles_cut": cs["cycles_cut"], "cycle_rounds": cs["cycle_rounds"], "depth_rounds": cs["depth_rounds"],
+                        "extent_sum": cs["extent_sum"]}
+        for kind in ("file", "topology"):
+            f, kms = per[kind]["found"], np.array(per[kind]["ms"])
+            khave = [i for i in range(len(reads)) if f.seeds[i]]
+            a_ms, a_jobs, a_ok = aligner_kernel_ms([reads[i] for i in khave], [f.seeds[i] for i in khave])
+            ksup = [s[0] for s in f.support if s]
+            row["coord"][kind] = {"find_seeds_loci_kernel_ms": ms_row(kms), "seeds": sum(len(s) for s in f.seeds),
+                                  "reads_with_two_seeds": sum(1 for s in f.seeds if len(s) > 1), "reads_without_seed": len(reads) - len(khave),
+                                  "mean_support_of_first_seed": round(float(np.mean(ksup)), 1) if ksup else 0.0,
+                                  "aligner": {"kernel_ms": round(a_ms, 3), "jobs": a_jobs, "reads_aligned": a_ok},
+                                  "seeding_plus_aligner_ms": round(float(np.median(kms)) + a_ms, 3)}
     if args.max_walks:
         row["walk"] = {key: int(v) for key, v in walk.items()}
         row["in_node"] = in_node
