@@ -184,7 +184,22 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
             cs = seeder.seed_coord_stats()
             out.write("seed coordinate: topology, %d trees, %d cycles cut, %d + %d rounds\n" % (cs["trees"], cs["cycles_cut"], cs["cycle_rounds"], cs["depth_rounds"]))
         by_locus = getattr(params, "seedLoci", False)
-        found = seeder.find_seeds([r.sequence for r in reads], loci=by_locus, max_seeds=params.seedMax)
+        # seeds and job plan on the device from one upload of the reads (Graph.prepare_seeded), in the order the reads are aligned in;
+        # a library or back end without that goes the two-call way
+        seeded = None
+        if seeder is graph:
+            try:
+                seeded = graph.prepare_seeded([r.sequence for r in reads[::-1]], dict(max_seeds=params.seedMax), by_locus,
+                                              params.initialBandwidth, params.rampBandwidth, flags=binding.GA_F_TRACE)
+            except binding.SeededUnsupported:
+                seeded = None
+        if seeded is not None:
+            found = seeded.seeds()
+            for field in ("seeds", "support", "n_hits", "truncated", "locus_hits", "locus_span", "n_loci"):     # (back into the reads' order)
+                if getattr(found, field) is not None:
+                    setattr(found, field, getattr(found, field)[::-1])
+        else:
+            found = seeder.find_seeds([r.sequence for r in reads], loci=by_locus, max_seeds=params.seedMax)
         seeds_of = {i: s for i, s in enumerate(found.seeds) if s}
         out.write("seeds found for %d of %d reads\n" % (len(seeds_of), len(reads)))
         if by_locus:
@@ -194,7 +209,15 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
     order = list(range(len(reads)))[::-1]
     with_seeds = [i for i in order if i in seeds_of]
     results = {}
-    if with_seeds:
+    if find_seeds and seeded is not None:
+        try:
+            seeded.run()
+            for i, r in zip(order, seeded.collect()):
+                if i in seeds_of:
+                    results[i] = r
+        finally:
+            seeded.close()
+    elif with_seeds:
         batch = graph.prepare([reads[i].sequence for i in with_seeds], [seeds_of[i] for i in with_seeds],
                               params.initialBandwidth, params.rampBandwidth, flags=binding.GA_F_TRACE)
         batch.run()

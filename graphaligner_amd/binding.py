@@ -80,6 +80,11 @@ class GaSeedCoordStats(C.Structure):
                 ("reserved", C.c_uint32), ("extent_sum", C.c_uint64), ("build_ms", C.c_double)]
 
 
+class GaBatchPrepareStats(C.Structure):
+    _fields_ = [("seed_kernel_ms", C.c_double), ("plan_kernel_ms", C.c_double), ("eq_kernel_ms", C.c_double), ("host_ms", C.c_double),
+                ("n_seeds", C.c_uint64), ("n_jobs", C.c_uint64), ("reads_without_seed", C.c_uint64)]
+
+
 SEED_COORDINATES = {"file": 0, "topology": 1}
 
 
@@ -165,6 +170,13 @@ def load(path=None):
             L.ga_graph_seed_coordinate_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.ga_seed_set_free.argtypes = [C.c_void_p]
         L.ga_seed_set_free.restype = None
+    if hasattr(L, "ga_batch_plan_copy"):                                   # (bench.py --lib may name a build from before seeded batches)
+        L.ga_batch_plan_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]
+        L.ga_batch_prepare_seeded.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+        L.ga_align_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+        L.ga_batch_prepare_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "ga_batch_seeds"):
+            L.ga_batch_seeds.argtypes = [C.c_void_p, C.c_void_p]
     _libs[path] = L
     return L
 
@@ -285,6 +297,36 @@ class Graph:
                                                        offs.ctypes.data_as(C.c_void_p), n), "ga_graph_seed_index_copy")
         return keys[:n], nodes[:n], offs[:n]
 
+    def _seed_params(self, params, what, need_index=True):
+        """ga_seed_params_t: the defaults, k and sample_shift of the index, then the fields `params` names.  need_index=False: without
+        an index the defaults stay, and the call the parameters go to says that the index is missing"""
+        p = GaSeedParams()
+        self.L.ga_seed_params_default(C.byref(p))
+        st = GaSeedIndexStats()
+        status = self.L.ga_graph_seed_index_stats(self.h, C.byref(st))
+        if need_index:
+            _check(self.L, status, "ga_graph_seed_index_stats")
+        if status == 0:
+            p.k, p.sample_shift = st.k, st.sample_shift
+        for name, v in (params or {}).items():
+            if name not in dict(GaSeedParams._fields_):
+                raise TypeError("%s: unknown parameter %s" % (what, name))
+            setattr(p, name, int(v))
+        return p
+
+    # ---- seeded batches (include/graphaligner_amd.h: ga_batch_prepare_seeded) ----
+    def prepare_seeded(self, reads, params=None, loci=False, bw=35, ramp=0, flags=0, names=None):
+        """a batch whose seeds are found and whose jobs are planned on the device, from one upload of the reads: what
+        prepare(reads, find_seeds(reads, loci, **params).seeds, ...) gives, without the round trip.  reads: list of str or a ReadSet
+        (its seeds are ignored); params: dict of the ga_seed_params_t fields that differ from the defaults.  A library or back end
+        without the feature raises SeededUnsupported."""
+        return Batch(self, reads, None, bw, ramp, flags, names, find_seeds=dict(params=params, loci=loci))
+
+    def align_reads(self, reads, params=None, loci=False, bw=35, ramp=0, flags=0):
+        b = self.prepare_seeded(reads, params, loci, bw, ramp, flags)
+        b.run()
+        return b.collect()
+
     def find_seeds(self, reads, loci=False, **params):
         """reads: list of str.  params: fields of ga_seed_params_t that differ from the defaults (k and sample_shift default to the index's).
         Returns a SeedResult: .seeds = per read a list of (node, pos, reverse), as Graph.prepare / align take them, and the diagnostics.
@@ -293,14 +335,7 @@ class Graph:
         self._need_seeding()
         if loci and not hasattr(self.L, "ga_find_seeds_loci"):
             raise RuntimeError("this library has no ga_find_seeds_loci")
-        p = GaSeedParams()
-        self.L.ga_seed_params_default(C.byref(p))
-        st = self.seed_index_stats()
-        p.k, p.sample_shift = st["k"], st["sample_shift"]
-        for name, v in params.items():
-            if name not in dict(GaSeedParams._fields_):
-                raise TypeError("find_seeds: unknown parameter %s" % name)
-            setattr(p, name, int(v))
+        p = self._seed_params(params, "find_seeds")
         n = len(reads)
         keep = [r.encode() if isinstance(r, str) else r for r in reads]
         arr = (GaRead * max(n, 1))()
@@ -314,26 +349,34 @@ class Graph:
         else:
             _check(self.L, self.L.ga_find_seeds(self.h, arr, n, C.byref(p), C.byref(out)), "ga_find_seeds")
         try:
-            S = out.contents
-            offs = np.ctypeslib.as_array(S.seed_offsets, shape=(n + 1,)).astype(np.int64) if n else np.zeros(1, dtype=np.int64)
-            total = int(offs[-1])
-            res = SeedResult()
-            flat = [(S.seeds[i].node_id, S.seeds[i].read_pos, bool(S.seeds[i].reverse)) for i in range(total)]
-            sup = [int(S.support[i]) for i in range(total)]
-            res.seeds = [flat[offs[i]:offs[i + 1]] for i in range(n)]
-            res.support = [sup[offs[i]:offs[i + 1]] for i in range(n)]
-            res.n_hits = [int(S.n_hits[i]) for i in range(n)]
-            res.truncated = [bool(S.truncated[i]) for i in range(n)]
-            res.kernel_ms = S.kernel_ms
-            if loci:
-                size = [int(S.locus_hits[i]) for i in range(total)]
-                span = [(int(S.locus_first_p[i]), int(S.locus_last_p[i])) for i in range(total)]
-                res.locus_hits = [size[offs[i]:offs[i + 1]] for i in range(n)]
-                res.locus_span = [span[offs[i]:offs[i + 1]] for i in range(n)]
-                res.n_loci = [int(S.n_loci[i]) for i in range(n)]
-            return res
+            return _seed_result(out.contents, n, loci)
         finally:
             self.L.ga_seed_set_free(out)
+
+
+class SeededUnsupported(RuntimeError):
+    """ga_batch_prepare_seeded is missing from the library, or it refused with GA_E_INVALID (a back end without the feature, no seed
+    index, parameters that do not fit the index): callers with a two-call path fall back to it"""
+
+
+def _seed_result(S, n, loci):
+    offs = np.ctypeslib.as_array(S.seed_offsets, shape=(n + 1,)).astype(np.int64) if n else np.zeros(1, dtype=np.int64)
+    total = int(offs[-1])
+    res = SeedResult()
+    flat = [(S.seeds[i].node_id, S.seeds[i].read_pos, bool(S.seeds[i].reverse)) for i in range(total)]
+    sup = [int(S.support[i]) for i in range(total)]
+    res.seeds = [flat[offs[i]:offs[i + 1]] for i in range(n)]
+    res.support = [sup[offs[i]:offs[i + 1]] for i in range(n)]
+    res.n_hits = [int(S.n_hits[i]) for i in range(n)]
+    res.truncated = [bool(S.truncated[i]) for i in range(n)]
+    res.kernel_ms = S.kernel_ms
+    if loci:
+        size = [int(S.locus_hits[i]) for i in range(total)]
+        span = [(int(S.locus_first_p[i]), int(S.locus_last_p[i])) for i in range(total)]
+        res.locus_hits = [size[offs[i]:offs[i + 1]] for i in range(n)]
+        res.locus_span = [span[offs[i]:offs[i + 1]] for i in range(n)]
+        res.n_loci = [int(S.n_loci[i]) for i in range(n)]
+    return res
 
 
 class SeedResult:
@@ -376,15 +419,27 @@ class ReadSet:
 
 
 class Batch:
-    def __init__(self, graph, reads, seeds, bw, ramp, flags, names=None):
+    def __init__(self, graph, reads, seeds, bw, ramp, flags, names=None, find_seeds=None):
         self.g = graph
         L = self.L = graph.L
-        rs = reads if isinstance(reads, ReadSet) else ReadSet(reads, seeds, names)
+        self.loci = None                   # a seeded batch: whether its seeds are per locus
+        rs = reads if isinstance(reads, ReadSet) else ReadSet(reads, seeds if find_seeds is None else [[]] * len(reads), names)
         self._rs = rs                      # (the arrays must outlive the batch: GAM encoding reads the names)
         self._arr, self._sarr, self._offs = rs.arr, rs.sarr, rs.offs
         self.n_reads = rs.n_reads
         self.total_bp = rs.total_bp
         h = C.c_void_p()
+        if find_seeds is not None:
+            if not hasattr(L, "ga_batch_prepare_seeded") or not hasattr(L, "ga_find_seeds"):
+                raise SeededUnsupported("this library has no ga_batch_prepare_seeded")
+            p = graph._seed_params(find_seeds.get("params"), "prepare_seeded", need_index=False)
+            self.loci = bool(find_seeds.get("loci"))
+            st = L.ga_batch_prepare_seeded(graph.h, rs.arr, rs.n_reads, C.byref(p), int(self.loci), bw, ramp, flags, C.byref(h))
+            if st == 100:
+                raise SeededUnsupported("ga_batch_prepare_seeded failed: %s (%d)" % (L.ga_status_string(st).decode(), st))
+            _check(L, st, "ga_batch_prepare_seeded")
+            self.h = h
+            return
         _check(L, L.ga_batch_prepare(graph.h, rs.arr, rs.n_reads, rs.sarr, rs.offs.ctypes.data_as(C.c_void_p), bw, ramp, flags, C.byref(h)), "ga_batch_prepare")
         self.h = h
 
@@ -397,6 +452,43 @@ class Batch:
         d = {k: getattr(st, k) for k, _ in st._fields_}
         d["stamps"] = list(st.stamps)
         return d
+
+    def seeds(self):
+        """the SeedResult a seeded batch was planned from (what Graph.find_seeds would have returned); an error for other batches"""
+        out = C.POINTER(GaSeedSetLoci if self.loci else GaSeedSet)()
+        _check(self.L, self.L.ga_batch_seeds(self.h, C.byref(out)), "ga_batch_seeds")
+        try:
+            return _seed_result(out.contents, self.n_reads, bool(self.loci))
+        finally:
+            self.L.ga_seed_set_free(out)
+
+    def plan(self):
+        """the job plan of any batch, for tests and tools: dict(jobs=..., seeds=..., fills=...) of numpy record arrays with the fields of
+        ga_batch_plan_copy"""
+        counts = (C.c_size_t * 3)()
+        nul = [None]
+        _check(self.L, self.L.ga_batch_plan_copy(self.h, *(nul * 4), 0, *(nul * 6), 0, *(nul * 6), 0, counts), "ga_batch_plan_copy")
+        nj, ns, nf = (int(c) for c in counts)
+        jobs = np.zeros(nj, dtype=[("rows_off", "<u8"), ("n_rows", "<u4"), ("seed_node", "<u4"), ("trace_rows", "<u4")])
+        seeds = np.zeros(ns, dtype=[("pos", "<u8"), ("seedNodeIndex", "<u4"), ("early", "<i4"), ("valid", "u1"), ("bwJob", "<i8"), ("fwJob", "<i8")])
+        fills = np.zeros(nf, dtype=[("read", "<u8"), ("off", "<u8"), ("n", "<u8"), ("padded", "<u8"), ("pos", "<u8"), ("backward", "u1")])
+        cols = []
+        for arr, cap in ((jobs, nj), (seeds, ns), (fills, nf)):
+            tmp = [np.ascontiguousarray(arr[name]) for name in arr.dtype.names]
+            cols.append(tmp)
+        args = [c.ctypes.data_as(C.c_void_p) for c in cols[0]] + [nj] + [c.ctypes.data_as(C.c_void_p) for c in cols[1]] + [ns] + \
+               [c.ctypes.data_as(C.c_void_p) for c in cols[2]] + [nf]
+        _check(self.L, self.L.ga_batch_plan_copy(self.h, *args, None), "ga_batch_plan_copy")
+        for arr, tmp in zip((jobs, seeds, fills), cols):
+            for name, col in zip(arr.dtype.names, tmp):
+                arr[name] = col
+        return dict(jobs=jobs, seeds=seeds, fills=fills)
+
+    def prepare_stats(self):
+        """ga_batch_prepare_stats_t of a seeded batch as a dict"""
+        st = GaBatchPrepareStats()
+        _check(self.L, self.L.ga_batch_prepare_stats(self.h, C.byref(st)), "ga_batch_prepare_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     def collect_gam(self, halve_node_ids=True):
         """align results as the bytes of a GAM file (what the reference's driver writes, Aligner.cpp:301-314)"""

@@ -118,10 +118,47 @@ public:
 	virtual int copyLin(int64_t*, size_t) const { return 100; }
 };
 
+// ---- seeded batches (ga_plan.h): seeds found and jobs planned on the back end's side, from one upload of the reads ---------------
+// what the host hands over: the batch's block (reads in the seeder's layout -- every read at a multiple of 16 with 16 bytes of padding
+// behind it --, then the read records and the hand-out order, as DevSeedEngine lays a batch out), the graph's twin table and the tables
+struct GaSeededRequest
+{
+	const char* block = nullptr;
+	size_t seqBytes = 0, oRecs = 0, oOrder = 0, blockBytes = 0;   // (offsets of the records and the order inside the block; its used size)
+	size_t nReads = 0;
+	GaSeedParams p{};
+	bool byLocus = false;
+	uint32_t overlap = 0;
+	const uint32_t* twin = nullptr; const uint8_t* rev = nullptr;       // per node (ga_plan.h: PlanLaunch)
+	const uint8_t* hasComplement = nullptr;                             // 256 entries
+	const uint8_t* rowCode = nullptr; const uint8_t* rowCodeRc = nullptr; uint8_t padCode = 0;
+	uint64_t rowsBound = 0;                                             // no plan of these reads has more rows (padded) than this
+};
+// what comes back, in one download: pointers into a block that `keep` holds
+struct GaSeededPlan
+{
+	std::shared_ptr<char> keep;
+	const uint32_t* outN = nullptr;        // [nReads][3] seeds, hits used, truncated
+	const uint32_t* outSeed = nullptr;     // [nReads][max_seeds][3] node index, read position, support
+	const uint32_t* outLocus = nullptr;    // by locus: [nReads][max_seeds][3]
+	const uint32_t* outNLoci = nullptr;    // by locus: [nReads]
+	const GaPlanSeed* seeds = nullptr;     // [nReads][max_seeds]
+	const GaJob* jobs = nullptr; const GaEqFill* fills = nullptr; const uint32_t* fillRead = nullptr; size_t nJobs = 0;
+	const uint8_t* badFills = nullptr;     // per fill: a row outside IUPAC (back ends that build the match words; else null)
+	uint64_t rowsTotal = 0;
+	double seed_ms = 0, plan_ms = 0, eq_ms = 0;
+};
+
+// (see ga_backend_create_batch below)
+typedef std::function<const std::vector<uint8_t>&()> GaRowsProvider;
+class GaBackendBatch;
 class GaBackendGraph
 {
 public:
 	virtual ~GaBackendGraph() {}
+	// first half of a seeded batch: upload, seeding, plan, match words (where the back end builds them), download.  The batch it returns
+	// runs once finishSeeded has been given the host's copy of the jobs.  A back end without the feature refuses (100 = GA_E_INVALID)
+	virtual GaBackendBatch* beginSeededBatch(const GaSeededRequest&, GaSeededPlan&, int* status) { *status = 100; return nullptr; }
 	// nullptr: this back end has no seeding (the alignment-only host emulation of tests/emul)
 	virtual GaSeedEngine* seedEngine() { return nullptr; }
 	// true: ga_backend_create_batch wants a GaEqSource and builds the match words on its side (the product: a kernel over the uploaded
@@ -140,6 +177,8 @@ class GaBackendBatch
 {
 public:
 	virtual ~GaBackendBatch() {}
+	// second half of a seeded batch (GaBackendGraph::beginSeededBatch); eq: the finished match words for a back end that does not build them
+	virtual int finishSeeded(const std::vector<GaJob>&, const GaRunConfig&, GaRowsProvider, const uint64_t*, size_t) { return 100; }
 	// back ends that build the match words: per fill of the GaEqSource, 1 when one of its rows is a character outside IUPAC
 	virtual const std::vector<uint8_t>* invalidFills() const { return nullptr; }
 	// GaRunConfig::emit_runs as it ended up (a back end that builds the match words clears it when a row is such a character)
@@ -156,13 +195,24 @@ struct ga_graph;
 struct GaGraphView { bool finalized; const std::vector<int64_t>* ids; const GaFlatGraph* flat; GaBackendGraph* device; };
 GaGraphView ga_graph_view(const ga_graph* g);
 
+// what ga_batch_seeds (ga_seed_host.cpp) needs of a batch made by ga_batch_prepare_seeded, which is ga_host.cpp's own
+struct ga_batch;
+struct GaBatchSeedView
+{
+	bool seeded = false, byLocus = false;
+	const ga_graph* g = nullptr;
+	size_t nReads = 0; uint32_t maxSeeds = 0;
+	const uint32_t* outN = nullptr; const uint32_t* outSeed = nullptr; const uint32_t* outLocus = nullptr; const uint32_t* outNLoci = nullptr;
+	double kernel_ms = 0;
+};
+GaBatchSeedView ga_batch_seed_view(const ga_batch* b);
+
 // returns nullptr + sets *status (GA_E_NO_DEVICE ...) on failure
 GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& g, const GaHmmTables& hmm, int device, int* status);
 // eq: per job and 64-row slice five 64-bit words (job j, slice s at (jobs[j].rows_off / 64 + s) * 5): the match words of the slice's rows
 // against A, C, G, T and a meta word (bits 0-2 exact-compare code of the slice's last row, bit 3 = a row with an invalid character)
 // rows: the row codes (one byte per padded read base) are only needed by the wave-per-read ladder kernels, so they are built and uploaded
 // on demand: the provider returns them (building them at its first call)
-typedef std::function<const std::vector<uint8_t>&()> GaRowsProvider;
 // (eq or src: the finished words, or what a back end that builds them itself builds them from)
 GaBackendBatch* ga_backend_create_batch(GaBackendGraph* g, GaRowsProvider rows, const uint64_t* eq, const GaEqSource* src, size_t eqWords, const std::vector<GaJob>& jobs,
                                         const GaRunConfig& cfg, int* status);

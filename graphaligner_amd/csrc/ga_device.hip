@@ -18,6 +18,7 @@
 #include "ga_kernel.h"
 #include "ga_lanes.h"
 #include "ga_seed_dev.h"
+#include "ga_plan.h"
 
 namespace {
 
@@ -227,8 +228,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
 // slice in hand: the character's row code through a 512-byte table in LDS, four ballots = the slice's match words against A, C, G, T
 // (characterMatch, GraphAligner.h:2039-2110; what the reference builds as EqVector, :2338-2351), one more for "a row outside IUPAC".
 // The row codes themselves (one byte per padded row: what the wave-per-read kernels read) are written on the way.
-__global__ void __launch_bounds__(64) ga_eq_words_kernel(const uint8_t* __restrict__ seq, const GaEqFill* __restrict__ fills, uint32_t nFills, const uint8_t* __restrict__ lut,
-                                                         uint32_t padCode, uint64_t* __restrict__ eq, uint8_t* __restrict__ flags, uint8_t* __restrict__ rows)
+__device__ __forceinline__ void eq_words_body(const uint8_t* __restrict__ seq, const GaEqFill* __restrict__ fills, uint32_t nFills, const uint8_t* __restrict__ lut,
+                                              uint32_t padCode, uint64_t* __restrict__ eq, uint8_t* __restrict__ flags, uint8_t* __restrict__ rows)
 {
 	__shared__ uint8_t t[512];
 	const uint32_t lane = threadIdx.x;
@@ -254,6 +255,46 @@ __global__ void __launch_bounds__(64) ga_eq_words_kernel(const uint8_t* __restri
 		}
 		if (lane == 0) flags[fi] = bad ? 1 : 0;
 	}
+}
+__global__ void __launch_bounds__(64) ga_eq_words_kernel(const uint8_t* __restrict__ seq, const GaEqFill* __restrict__ fills, uint32_t nFills, const uint8_t* __restrict__ lut,
+                                                         uint32_t padCode, uint64_t* __restrict__ eq, uint8_t* __restrict__ flags, uint8_t* __restrict__ rows)
+{
+	eq_words_body(seq, fills, nFills, lut, padCode, eq, flags, rows);
+}
+// the same over fills that the plan kernels left in device memory (ga_plan.h): their number is the plan's first total, read on the device
+__global__ void __launch_bounds__(64) ga_eq_words_planned_kernel(const uint8_t* __restrict__ seq, const GaEqFill* __restrict__ fills, const uint64_t* __restrict__ totals,
+                                                                 const uint8_t* __restrict__ lut, uint32_t padCode, uint64_t* __restrict__ eq, uint8_t* __restrict__ flags,
+                                                                 uint8_t* __restrict__ rows)
+{
+	eq_words_body(seq, fills, (uint32_t)totals[0], lut, padCode, eq, flags, rows);
+}
+
+// ---- the job plan of a seeded batch (ga_plan.h): three launches around two scans -------------------------------------------------
+// one wave per read at a time: first_bad[read]
+__global__ void __launch_bounds__(64) ga_plan_first_bad_kernel(gap::PlanLaunch L, const uint8_t* __restrict__ hasComplement)
+{
+	__shared__ uint8_t t[256];
+	const uint32_t lane = threadIdx.x;
+	for (uint32_t i = lane; i < 256; i += 64) t[i] = hasComplement[i];
+	__syncthreads();
+	for (uint32_t r = blockIdx.x; r < L.n_reads; r += gridDim.x)
+	{
+		uint32_t bad = gap::first_bad_lane(L, t, r, lane);
+		for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)bad, d, 64); bad = o < bad ? o : bad; }
+		if (lane == 0) L.first_bad[r] = bad;
+	}
+}
+// one lane per seed slot, and one more for the scans' last element
+__global__ void __launch_bounds__(256) ga_plan_slot_kernel(gap::PlanLaunch L)
+{
+	const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (s <= (uint64_t)L.n_reads * L.max_seeds) gap::plan_slot(L, (uint32_t)s);
+}
+__global__ void __launch_bounds__(256) ga_plan_write_kernel(gap::PlanLaunch L)
+{
+	const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x, nSlots = (uint64_t)L.n_reads * L.max_seeds;
+	if (s < nSlots) gap::plan_write(L, (uint32_t)s);
+	else if (s == nSlots) gap::plan_tail(L);
 }
 
 // every job's output record starts a run as "not run" (what a job keeps when no pass ever picks it up)
@@ -309,6 +350,12 @@ struct DevGraph : GaBackendGraph
 	// seeding (ga_seed.h): the k-mer index of this graph and its buffers, built on request
 	std::unique_ptr<gasd::DevSeedEngine> seed;
 	GaSeedEngine* seedEngine() override { return seed.get(); }
+
+	// seeded batches (ga_plan.h): twin[n] and digraph id & 1 per node, uploaded at the first seeded prepare, freed with the graph
+	std::mutex twinLock;
+	uint32_t* dTwin = nullptr;
+	uint8_t* dRev = nullptr;
+	GaBackendBatch* beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status) override;
 
 	int device = 0;
 	GaDevGraph g;
@@ -460,7 +507,14 @@ struct DevBatch : GaBackendBatch
 		if (privateScratch) hipFree(privateScratch);
 		if (evA) hipEventDestroy(evA);
 		if (evB) hipEventDestroy(evB);
+		for (hipEvent_t e : evP) if (e) hipEventDestroy(e);
 		if (stream) hipStreamDestroy(stream);
+	}
+	// a block of alloc() that the batch no longer needs, handed back before the batch ends
+	void release(void* p)
+	{
+		for (size_t i = 0; i < allocs.size(); i++)
+			if (allocs[i].second == p) { g->giveBlock(p, allocs[i].first); allocs.erase(allocs.begin() + (long)i); return; }
 	}
 	template <typename T> int alloc(T** out, size_t count)
 	{
@@ -489,21 +543,33 @@ struct DevBatch : GaBackendBatch
 	const std::vector<uint8_t>* invalidFills() const override { return &badFills; }
 	bool emittingRuns() const override { return cfg.emit_runs != 0; }
 
-	int init(const uint64_t* eq, const GaEqSource* src, size_t eqWords, const std::vector<GaJob>& jobsIn)
+	// the stream and the events, before anything else
+	int open()
 	{
 		HIP_OK(hipSetDevice(g->device));
 		// (non-blocking: a copy or a kernel of this batch must not wait for another batch's kernel through the null stream)
 		HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
 		HIP_OK(hipEventCreate(&evA));
 		HIP_OK(hipEventCreate(&evB));
-		jobs = jobsIn;
 		memset(&L, 0, sizeof(L));
 		L.graph = g->g;
 		L.hmm = g->hmm;
+		return 0;
+	}
+	// what every pass shares of the jobs and the configuration
+	void setJobs(const std::vector<GaJob>& jobsIn)
+	{
+		jobs = jobsIn;
 		L.n_jobs = (uint32_t)jobs.size();
 		L.initial_bw = cfg.initial_bw;
 		L.ramp_bw = cfg.ramp_bw;
 		L.max_slices = std::max<uint32_t>(cfg.max_slices, 1);
+	}
+
+	int init(const uint64_t* eq, const GaEqSource* src, size_t eqWords, const std::vector<GaJob>& jobsIn)
+	{
+		if (int s = open()) return s;
+		setJobs(jobsIn);
 		GaJob* dJobs; uint64_t* eqDev;
 		if (alloc(&eqDev, eqWords)) return GA_E_DEVICE;
 		if (alloc(&dJobs, jobs.size())) return GA_E_DEVICE;
@@ -538,6 +604,12 @@ struct DevBatch : GaBackendBatch
 		L.rows = nullptr;
 		L.jobs = dJobs;
 		dEq = eqDev;
+		return finish();
+	}
+
+	// the hand-out order, the output records and the trace pool, from the host's copy of the jobs
+	int finish()
+	{
 		// the device queues hand jobs out longest first: the short ones fill the tail of a launch, and the 64 jobs a lanes = reads
 		// wave carries together have similar lengths
 		orderHost.resize(jobs.size());
@@ -562,6 +634,140 @@ struct DevBatch : GaBackendBatch
 		if (alloc(&L.traces, L.trace_pool_cap)) return GA_E_DEVICE;
 		HIP_OK(hipStreamSynchronize(stream));
 		return 0;
+	}
+
+	// ---- seeded batch (ga_plan.h): everything from the one upload of the reads to the one download of seeds and plan ----------------
+	uint8_t planLut[768];              // row codes, row codes of the complement, "has a complement": lives as long as its upload may run
+	hipEvent_t evP[4] = {nullptr, nullptr, nullptr, nullptr};
+	int beginSeeded(const GaSeededRequest& req, GaSeededPlan& plan)
+	{
+		if (int s = open()) return s;
+		gasd::DevSeedEngine* eng = g->seed.get();
+		if (!eng || !eng->built()) return GA_E_INVALID;
+		const size_t nReads = req.nReads, nSlots = nReads * req.p.max_seeds, nJobsCap = 2 * nSlots;
+		if (nSlots >= ((size_t)1 << 30)) return GA_E_INVALID;                  // (slot and job numbers are 32-bit)
+		for (hipEvent_t& e : evP) HIP_OK(hipEventCreate(&e));
+		auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+		// what comes back in the one download
+		const size_t oOutN = 0, oOutSeed = oOutN + up(nReads * 12), oOutLocus = oOutSeed + up(nSlots * 12), oOutNLoci = oOutLocus + (req.byLocus ? up(nSlots * 12) : 0);
+		const size_t oTotals = oOutNLoci + (req.byLocus ? up(nReads * 4) : 0), oSeeds = oTotals + 256, oJobs = oSeeds + up(nSlots * sizeof(GaPlanSeed));
+		const size_t oFills = oJobs + up(nJobsCap * sizeof(GaJob)), oFillRead = oFills + up(nJobsCap * sizeof(GaEqFill)), oFlags = oFillRead + up(nJobsCap * 4);
+		const size_t downBytes = oFlags + up(nJobsCap);
+		// what stays: the reads' block, and the plan's work arrays
+		const size_t oFirstBad = 0, oNBw = oFirstBad + up(nReads * 4), oNFw = oNBw + up((nSlots + 1) * 4), oSlotJobs = oNFw + up((nSlots + 1) * 4);
+		const size_t oJobAt = oSlotJobs + up((nSlots + 1) * 4), oSlotRows = oJobAt + up((nSlots + 1) * 4), oRowsAt = oSlotRows + up((nSlots + 1) * 8);
+		const size_t workBytes = oRowsAt + up((nSlots + 1) * 8);
+		const size_t eqWords = (size_t)(req.rowsBound / 64 + 1) * 5, rowBytes = (size_t)req.rowsBound + 128;
+		uint8_t *dIn, *dDown, *dWork, *dLut, *dRows; uint64_t* eqDev;
+		if (alloc(&dIn, req.blockBytes + 64) || alloc(&dDown, downBytes) || alloc(&dWork, workBytes) || alloc(&dLut, 768) || alloc(&dRows, rowBytes) || alloc(&eqDev, eqWords)) return GA_E_DEVICE;
+		{
+			std::lock_guard<std::mutex> guard(g->twinLock);
+			if (!g->dTwin)
+			{
+				void* tw = nullptr; void* rv = nullptr;
+				HIP_OK(hipMalloc(&tw, (size_t)g->g.n_nodes * 4));
+				g->allocs.push_back(tw);
+				HIP_OK(hipMalloc(&rv, (size_t)g->g.n_nodes));
+				g->allocs.push_back(rv);
+				HIP_OK(hipMemcpyAsync(tw, req.twin, (size_t)g->g.n_nodes * 4, hipMemcpyHostToDevice, stream));
+				HIP_OK(hipMemcpyAsync(rv, req.rev, (size_t)g->g.n_nodes, hipMemcpyHostToDevice, stream));
+				HIP_OK(hipStreamSynchronize(stream));
+				g->dRev = (uint8_t*)rv;
+				g->dTwin = (uint32_t*)tw;
+			}
+		}
+		memcpy(planLut, req.rowCode, 256); memcpy(planLut + 256, req.rowCodeRc, 256); memcpy(planLut + 512, req.hasComplement, 256);
+		// the one upload: reads, read records, hand-out order
+		HIP_OK(hipMemcpyAsync(dIn, req.block, req.blockBytes, hipMemcpyHostToDevice, stream));
+		HIP_OK(hipMemcpyAsync(dLut, planLut, 768, hipMemcpyHostToDevice, stream));
+		HIP_OK(hipMemsetAsync(dDown, 0, oTotals + 256, stream));                   // (the seeding kernel adds to cleared outputs)
+		gap::PlanLaunch P;
+		memset(&P, 0, sizeof(P));
+		P.node_start = g->g.node_start; P.twin = g->dTwin; P.rev = g->dRev;
+		P.n_nodes = g->g.n_nodes; P.n_reads = (uint32_t)nReads; P.max_seeds = req.p.max_seeds; P.overlap = req.overlap;
+		P.seq = dIn; P.reads = (const gas::SeedRead*)(dIn + req.oRecs);
+		P.out_n = (const uint32_t*)(dDown + oOutN); P.out_seed = (const uint32_t*)(dDown + oOutSeed);
+		P.first_bad = (uint32_t*)(dWork + oFirstBad); P.n_bw = (uint32_t*)(dWork + oNBw); P.n_fw = (uint32_t*)(dWork + oNFw);
+		P.slot_jobs = (uint32_t*)(dWork + oSlotJobs); P.job_at = (uint32_t*)(dWork + oJobAt); P.slot_rows = (uint64_t*)(dWork + oSlotRows); P.rows_at = (uint64_t*)(dWork + oRowsAt);
+		P.seeds = (GaPlanSeed*)(dDown + oSeeds); P.jobs = (GaJob*)(dDown + oJobs); P.fills = (GaEqFill*)(dDown + oFills); P.fill_read = (uint32_t*)(dDown + oFillRead);
+		P.totals = (uint64_t*)(dDown + oTotals); P.eq = eqDev; P.rows = dRows;
+		size_t tmpA = 0, tmpB = 0;
+		HIP_OK(rocprim::exclusive_scan(nullptr, tmpA, P.slot_jobs, P.job_at, 0u, nSlots + 1, rocprim::plus<uint32_t>(), stream));
+		HIP_OK(rocprim::exclusive_scan(nullptr, tmpB, P.slot_rows, P.rows_at, (uint64_t)0, nSlots + 1, rocprim::plus<uint64_t>(), stream));
+		uint8_t* dTmp;
+		if (alloc(&dTmp, std::max(tmpA, tmpB) + 16)) return GA_E_DEVICE;
+		plan.keep = g->hostBlock(downBytes);
+		if (!plan.keep) return GA_E_DEVICE;
+		{
+			// the engine's hit and label buffers are per graph: its lock is held until this stream has finished the seeding kernel
+			std::lock_guard<std::mutex> guard(eng->lock);
+			auto queue = [&]() -> int {
+			HIP_OK(hipEventRecord(evP[0], stream));
+			if (nReads)
+			{
+				if (int s = eng->launchResident(req.p, nReads, req.byLocus, dIn, P.reads, (const uint32_t*)(dIn + req.oOrder), (uint32_t*)(dDown + oOutN), (uint32_t*)(dDown + oOutSeed),
+				                                (uint32_t*)(dDown + oOutLocus), (uint32_t*)(dDown + oOutNLoci), stream)) return s;
+			}
+			HIP_OK(hipEventRecord(evP[1], stream));
+			if (nReads)
+			{
+				const uint32_t waves = (uint32_t)std::min<size_t>(nReads, (size_t)g->cus * 32);
+				hipLaunchKernelGGL(ga_plan_first_bad_kernel, dim3(waves), dim3(64), 0, stream, P, (const uint8_t*)(dLut + 512));
+			}
+			const uint32_t slotBlocks = (uint32_t)((nSlots + 1 + 255) / 256);
+			hipLaunchKernelGGL(ga_plan_slot_kernel, dim3(slotBlocks), dim3(256), 0, stream, P);
+			HIP_OK(rocprim::exclusive_scan(dTmp, tmpA, P.slot_jobs, P.job_at, 0u, nSlots + 1, rocprim::plus<uint32_t>(), stream));
+			HIP_OK(rocprim::exclusive_scan(dTmp, tmpB, P.slot_rows, P.rows_at, (uint64_t)0, nSlots + 1, rocprim::plus<uint64_t>(), stream));
+			hipLaunchKernelGGL(ga_plan_write_kernel, dim3(slotBlocks), dim3(256), 0, stream, P);
+			HIP_OK(hipEventRecord(evP[2], stream));
+			// the match words from the fills as they lie in device memory
+			if (nSlots)
+			{
+				const uint32_t blocks = (uint32_t)std::min<size_t>(nJobsCap, (size_t)g->cus * 64);
+				hipLaunchKernelGGL(ga_eq_words_planned_kernel, dim3(blocks), dim3(64), 0, stream, (const uint8_t*)dIn, (const GaEqFill*)P.fills, (const uint64_t*)P.totals, (const uint8_t*)dLut,
+				                   (uint32_t)req.padCode, eqDev, dDown + oFlags, dRows);
+			}
+			HIP_OK(hipGetLastError());
+			HIP_OK(hipEventRecord(evP[3], stream));
+			// the one download
+			HIP_OK(hipMemcpyAsync(plan.keep.get(), dDown, downBytes, hipMemcpyDeviceToHost, stream));
+			HIP_OK(hipEventSynchronize(evP[1]));
+			return 0;
+			};
+			// (a failure after the first launch: nothing of this batch may still run when the lock goes and the caller frees the batch,
+			// whose blocks and the graph's hit buffers the next prepare takes)
+			if (int s = queue()) { hipStreamSynchronize(stream); return s; }
+		}
+		HIP_OK(hipStreamSynchronize(stream));
+		// (the scans' arrays, their temporary storage and the tables serve the prepare only: back to the graph's block list now)
+		release(dWork); release(dTmp); release(dLut);
+		float ms[3] = {0, 0, 0};
+		for (int k = 0; k < 3; k++) HIP_OK(hipEventElapsedTime(&ms[k], evP[k], evP[k + 1]));
+		for (hipEvent_t& e : evP) { hipEventDestroy(e); e = nullptr; }
+		const char* h = plan.keep.get();
+		plan.outN = (const uint32_t*)(h + oOutN); plan.outSeed = (const uint32_t*)(h + oOutSeed);
+		if (req.byLocus) { plan.outLocus = (const uint32_t*)(h + oOutLocus); plan.outNLoci = (const uint32_t*)(h + oOutNLoci); }
+		plan.seeds = (const GaPlanSeed*)(h + oSeeds); plan.jobs = (const GaJob*)(h + oJobs); plan.fills = (const GaEqFill*)(h + oFills);
+		plan.fillRead = (const uint32_t*)(h + oFillRead); plan.badFills = (const uint8_t*)(h + oFlags);
+		const uint64_t* totals = (const uint64_t*)(h + oTotals);
+		plan.nJobs = (size_t)totals[0]; plan.rowsTotal = totals[1];
+		plan.seed_ms = ms[0]; plan.plan_ms = ms[1]; plan.eq_ms = ms[2];
+		if (plan.nJobs > nJobsCap || plan.rowsTotal > req.rowsBound) return GA_E_DEVICE;
+		badFills.assign(plan.badFills, plan.badFills + plan.nJobs);
+		builtRows = dRows;
+		L.rows = nullptr;
+		L.jobs = (const GaJob*)P.jobs;
+		dEq = eqDev;
+		return 0;
+	}
+	int finishSeeded(const std::vector<GaJob>& jobsIn, const GaRunConfig& c, GaRowsProvider rows, const uint64_t*, size_t) override
+	{
+		HIP_OK(hipSetDevice(g->device));
+		cfg = c;
+		rowsProvider = rows;
+		setJobs(jobsIn);
+		for (uint8_t f : badFills) if (f) { cfg.emit_runs = 0; break; }
+		return finish();
 	}
 
 	// scratch for one pass: the graph's pool, or a private allocation while another batch holds the pool
@@ -931,6 +1137,16 @@ GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& flat, const GaHmmTabl
 	g->seed = std::make_unique<gasd::DevSeedEngine>(g, device, g->cus, g->g);
 	*status = 0;
 	return g;
+}
+
+GaBackendBatch* DevGraph::beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status)
+{
+	DevBatch* b = new DevBatch();
+	b->g = this;
+	int s = b->beginSeeded(req, plan);
+	if (s) { delete b; *status = s; return nullptr; }
+	*status = 0;
+	return b;
 }
 
 GaBackendBatch* ga_backend_create_batch(GaBackendGraph* graph, GaRowsProvider rows, const uint64_t* eq, const GaEqSource* src, size_t eqWords, const std::vector<GaJob>& jobs,

@@ -102,6 +102,10 @@ struct ga_graph
 	GaFlatGraph flat;
 	GaHmmTables hmm;
 	GaBackendGraph* device = nullptr;
+	// per node index, made at Finalize for the plan of seeded batches (ga_plan.h): the node whose digraph id is this one's ^ 1
+	// (0xffffffff: there is none), and digraph id & 1
+	std::vector<uint32_t> twin;
+	std::vector<uint8_t> idOdd;
 	// optional node splitting (ga_graph_load_gfa_split): piece bigraph id -> the node it was cut from
 	struct Piece { int64_t orig; uint64_t start, len, origLen; };
 	std::unordered_map<int64_t, Piece> pieces;
@@ -187,6 +191,14 @@ static int finalizeGraph(ga_graph* g, int overlap)
 	g->ids.push_back(0); g->nodeStart.push_back(g->bases.size()); g->reverse.push_back(0); g->bases.push_back(4);
 	g->finalized = true;
 	const uint32_t n = g->nodeCount();
+	g->twin.assign(n, 0xffffffffu);
+	g->idOdd.assign(n, 0);
+	for (uint32_t i = 1; i + 1 < n; i++)
+	{
+		auto it = g->lookup.find(g->ids[i] ^ 1);
+		if (it != g->lookup.end()) g->twin[i] = it->second;
+		g->idOdd[i] = (uint8_t)(g->ids[i] & 1);
+	}
 	GaFlatGraph& f = g->flat;
 	f.node_start.assign(g->nodeStart.begin(), g->nodeStart.end());
 	f.node_start.push_back(g->bases.size());
@@ -324,6 +336,12 @@ struct ga_batch
 	GaBackendBatch* dev = nullptr;
 	bool ran = false;
 	uint64_t columnUpdates = 0, slicesRun = 0, rowsTotal = 0;
+	// a batch made by ga_batch_prepare_seeded: the seeding kernel's outputs as they were downloaded (ga_backend.h: GaSeededPlan) and the
+	// times of ga_batch_prepare_stats_t
+	bool seeded = false, byLocus = false;
+	GaSeedParams seedParams{};
+	std::vector<uint32_t> seedOutN, seedOut, seedOutLocus, seedNLoci;
+	double seedMs = 0, planMs = 0, eqMs = 0, hostMs = 0;
 	~ga_batch() { delete dev; }
 };
 
@@ -738,6 +756,50 @@ int ga_graph_upload(ga_graph_t* g, int device)
 int64_t ga_graph_node_count(const ga_graph_t* g) { return g ? g->nodeCount() : 0; }
 int64_t ga_graph_bp(const ga_graph_t* g) { return g ? (int64_t)g->bases.size() : 0; }
 
+// the match words built on the host, for a back end that wants them finished (the host emulations of tests/)
+static void buildHostWords(ga_batch* b)
+{
+	const CharTables& T = tables();
+	b->eq.reset(new uint64_t[b->eqWords]);
+	for (int k = 0; k < 5; k++) b->eq[b->eqWords - 5 + k] = 0;              // (the slack slice behind the last job)
+	forEachFill(b, [&](const ga_batch::RowFill& f, const ReadSeq& seq) {
+		// 64 row codes at a time, straight into the slice's match words
+		const uint8_t padCode = T.rowCode[(uint8_t)'N'];
+		const uint8_t* fw = (const uint8_t*)seq.data() + f.pos;
+		const uint8_t* bw = (const uint8_t*)seq.data() + f.n - 1;
+		uint8_t buf[W];
+		for (uint64_t r0 = 0; r0 < f.padded; r0 += W)
+		{
+			const uint64_t full = r0 + W <= f.n ? (uint64_t)W : r0 < f.n ? f.n - r0 : 0;
+			if (f.backward) for (uint64_t k = 0; k < full; k++) buf[k] = T.rowCodeRc[*(bw - (r0 + k))];
+			else for (uint64_t k = 0; k < full; k++) buf[k] = T.rowCode[fw[r0 + k]];
+			for (uint64_t k = full; k < (uint64_t)W; k++) buf[k] = padCode;
+			uint64_t* words = b->eq.get() + (f.off + r0) / W * 5;
+			ga_build_eq_words(buf, W, words);
+			if (words[4] & 8u) { b->anyInvalidRow.store(1, std::memory_order_relaxed); b->readInvalid[f.read].store(1, std::memory_order_relaxed); }
+		}
+	});
+}
+
+static void decideRuns(ga_batch* b)
+{
+	const ga_graph* g = b->g;
+	// Node runs instead of moves from the traceback when no result of the batch needs a cell list: no TraceItem lists wanted, every
+	// read with one seed at its first base (one forward job: no backward part to mirror, no later seed to test against the cells
+	// of an earlier one, GraphAligner.h:423-429), no character whose TraceItem the reference would assert on
+	{
+		// ... and a graph of long nodes (the shape the lanes = reads kernel is the first pass for): a path then changes node every few
+		// dozen rows and its runs are a fraction of its moves; on graphs chopped into short nodes moves are the smaller output
+		const double meanNode = g->nodeCount() > 2 ? (double)g->bases.size() / (double)(g->nodeCount() - 2) : 64.0;
+		// (with the words built by the back end, whether a row is such a character is known when the batch has been created: the back
+		// end clears the flag then)
+		bool runs = (b->flags & GA_F_TRACE) == 0 && b->anyInvalidRow.load() == 0 && meanNode >= 40 && !(getenv("GA_RUNS") && atoi(getenv("GA_RUNS")) == 0);
+		for (size_t i = 0; i < b->reads.size() && runs; i++) if (b->reads[i].nSeeds > 1) runs = false;
+		for (const SeedPlan& sp : b->seeds) if (sp.bwJob >= 0 || (sp.fwJob >= 0 && sp.pos != 0)) { runs = false; break; }
+		b->cfg.emit_runs = runs ? 1u : 0u;
+	}
+}
+
 int ga_batch_prepare(const ga_graph_t* g, const ga_read_t* reads, size_t nReads, const ga_seed_t* seeds, const size_t* seedOffsets,
                      int initialBandwidth, int rampBandwidth, uint32_t flags, ga_batch_t** out)
 {
@@ -876,40 +938,9 @@ int ga_batch_prepare(const ga_graph_t* g, const ga_read_t* reads, size_t nReads,
 	}
 	else
 	{
-	b->eq.reset(new uint64_t[b->eqWords]);
-	for (int k = 0; k < 5; k++) b->eq[b->eqWords - 5 + k] = 0;              // (the slack slice behind the last job)
-	forEachFill(b, [&](const RowFill& f, const ReadSeq& seq) {
-		// 64 row codes at a time, straight into the slice's match words
-		const uint8_t padCode = T.rowCode[(uint8_t)'N'];
-		const uint8_t* fw = (const uint8_t*)seq.data() + f.pos;
-		const uint8_t* bw = (const uint8_t*)seq.data() + f.n - 1;
-		uint8_t buf[W];
-		for (uint64_t r0 = 0; r0 < f.padded; r0 += W)
-		{
-			const uint64_t full = r0 + W <= f.n ? (uint64_t)W : r0 < f.n ? f.n - r0 : 0;
-			if (f.backward) for (uint64_t k = 0; k < full; k++) buf[k] = T.rowCodeRc[*(bw - (r0 + k))];
-			else for (uint64_t k = 0; k < full; k++) buf[k] = T.rowCode[fw[r0 + k]];
-			for (uint64_t k = full; k < (uint64_t)W; k++) buf[k] = padCode;
-			uint64_t* words = b->eq.get() + (f.off + r0) / W * 5;
-			ga_build_eq_words(buf, W, words);
-			if (words[4] & 8u) { b->anyInvalidRow.store(1, std::memory_order_relaxed); b->readInvalid[f.read].store(1, std::memory_order_relaxed); }
-		}
-	});
+	buildHostWords(b);
 	}
-	// Node runs instead of moves from the traceback when no result of the batch needs a cell list: no TraceItem lists wanted, every
-	// read with one seed at its first base (one forward job: no backward part to mirror, no later seed to test against the cells
-	// of an earlier one, GraphAligner.h:423-429), no character whose TraceItem the reference would assert on
-	{
-		// ... and a graph of long nodes (the shape the lanes = reads kernel is the first pass for): a path then changes node every few
-		// dozen rows and its runs are a fraction of its moves; on graphs chopped into short nodes moves are the smaller output
-		const double meanNode = g->nodeCount() > 2 ? (double)g->bases.size() / (double)(g->nodeCount() - 2) : 64.0;
-		// (with the words built by the back end, whether a row is such a character is known when the batch has been created: the back
-		// end clears the flag then)
-		bool runs = (flags & GA_F_TRACE) == 0 && b->anyInvalidRow.load() == 0 && meanNode >= 40 && !(getenv("GA_RUNS") && atoi(getenv("GA_RUNS")) == 0);
-		for (size_t i = 0; i < nReads && runs; i++) if (b->reads[i].nSeeds > 1) runs = false;
-		for (const SeedPlan& sp : b->seeds) if (sp.bwJob >= 0 || (sp.fwJob >= 0 && sp.pos != 0)) { runs = false; break; }
-		b->cfg.emit_runs = runs ? 1u : 0u;
-	}
+	decideRuns(b);
 	int status = GA_S_OK;
 	const auto tp2 = std::chrono::steady_clock::now();
 	GaEqSource src;
@@ -935,6 +966,209 @@ int ga_batch_prepare(const ga_graph_t* g, const ga_read_t* reads, size_t nReads,
 	return GA_S_OK;
 }
 
+// Seeds found and jobs planned on the back end's side (ga_plan.h): the host lays the reads out once, in the seeder's layout, and builds
+// its own records from what comes back in one download -- by copying, with no lookup and no pass over the characters.
+int ga_batch_prepare_seeded(const ga_graph_t* g, const ga_read_t* reads, size_t nReads, const ga_seed_params_t* params, int byLocus,
+                            int initialBandwidth, int rampBandwidth, uint32_t flags, ga_batch_t** out)
+{
+	if (!g || !out || (!reads && nReads)) return GA_E_INVALID;
+	if (!g->finalized) return GA_E_NOT_FINALIZED;
+	if (!g->device) return GA_E_NO_DEVICE;
+	GaSeedEngine* eng = g->device->seedEngine();
+	if (!eng || !eng->built()) return GA_E_INVALID;
+	GaSeedParams p{15, 2, 8, 4096, 1024, 64, 2, 2};                             // (ga_seed_params_default)
+	if (params) p = GaSeedParams{params->k, params->sample_shift, params->max_occ, params->max_hits, params->window, params->diag_tol, params->min_support, params->max_seeds};
+	if (!(p.k >= 11 && p.k <= 31 && p.sample_shift <= 8 && p.max_hits >= 1 && p.max_hits <= 65536 && p.max_seeds >= 1 && p.max_seeds <= 64)) return GA_E_INVALID;
+	if (eng->info().k != p.k || eng->info().sample_shift != p.sample_shift) return GA_E_INVALID;
+	for (size_t i = 0; i < nReads; i++) if ((reads[i].length && !reads[i].sequence) || reads[i].length > 0xfffffff0ull) return GA_E_INVALID;
+	const CharTables& T = tables();
+	const auto t0 = std::chrono::steady_clock::now();
+	std::unique_ptr<ga_batch> b(new ga_batch());
+	b->g = g;
+	b->flags = flags;
+	b->cfg.initial_bw = initialBandwidth;
+	b->cfg.ramp_bw = rampBandwidth;
+	b->seeded = true; b->byLocus = byLocus != 0; b->seedParams = p;
+	b->reads.resize(nReads);
+	b->names.resize(nReads);
+	b->seqs.resize(nReads);
+	// the block: every read at a multiple of 16 with 16 bytes of padding behind it, then the read records (offset, length) and the reads'
+	// numbers longest first, which is the order the seeding kernel hands them out in
+	struct Rec { uint64_t off; uint32_t len, reserved; };
+	std::vector<Rec> recs(nReads);
+	uint64_t seqBytes = 0, rowsBound = 0;
+	for (size_t i = 0; i < nReads; i++)
+	{
+		recs[i] = Rec{seqBytes, (uint32_t)reads[i].length, 0};
+		seqBytes += ((reads[i].length + 15) & ~(size_t)15) + 16;
+		// (a seed's two jobs have pad64(p + overlap) + pad64(length - p) rows)
+		rowsBound += (uint64_t)p.max_seeds * ((reads[i].length + (uint64_t)g->dbgOverlap + 128 + 63) / 64 * 64);
+	}
+	std::vector<uint32_t> order(nReads);
+	for (size_t i = 0; i < nReads; i++) order[i] = (uint32_t)i;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return reads[x].length > reads[y].length; });
+	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+	GaSeededRequest req;
+	req.seqBytes = (size_t)seqBytes; req.oRecs = up((size_t)seqBytes); req.oOrder = req.oRecs + up(nReads * sizeof(Rec)); req.blockBytes = req.oOrder + up(nReads * 4);
+	b->seqBufBytes = req.blockBytes + 64;
+	b->seqKeep = g->device->hostBlock(b->seqBufBytes);
+	if (!b->seqKeep) return GA_E_DEVICE;                                   // (no memory: not a refusal of the call)
+	b->seqBuf = b->seqKeep.get();
+	{
+		size_t nThreads = usableCores();
+		if (const char* e = getenv("GA_HOST_THREADS")) nThreads = (size_t)atoi(e);
+		nThreads = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(nThreads, 16), nReads / 256 + 1));
+		std::vector<std::thread> pool;
+		const size_t per = (nReads + nThreads - 1) / nThreads;
+		ga_batch* bp = b.get();
+		for (size_t t = 0; t < nThreads; t++)
+		{
+			const size_t lo = std::min(nReads, t * per), hi = std::min(nReads, lo + per);
+			if (lo < hi) pool.emplace_back([&, lo, hi, bp]() {
+				for (size_t i = lo; i < hi; i++)
+				{
+					char* at = bp->seqBuf + recs[i].off;
+					const size_t len = reads[i].length, room = ((len + 15) & ~(size_t)15) + 16;
+					if (len) memcpy(at, reads[i].sequence, len);
+					memset(at + len, 0, room - len);
+					bp->seqs[i] = ReadSeq(at, len);
+					bp->names[i] = reads[i].name ? reads[i].name : "";
+				}
+			});
+		}
+		for (auto& th : pool) th.join();
+	}
+	memset(b->seqBuf + seqBytes, 0, req.blockBytes - (size_t)seqBytes);
+	if (nReads) { memcpy(b->seqBuf + req.oRecs, recs.data(), nReads * sizeof(Rec)); memcpy(b->seqBuf + req.oOrder, order.data(), nReads * 4); }
+	uint8_t hasComplement[256];
+	for (int c = 0; c < 256; c++) hasComplement[c] = T.complement[c] ? 1 : 0;
+	req.block = b->seqBuf; req.nReads = nReads; req.p = p; req.byLocus = byLocus != 0; req.overlap = (uint32_t)g->dbgOverlap;
+	req.twin = g->twin.data(); req.rev = g->idOdd.data(); req.hasComplement = hasComplement;
+	req.rowCode = T.rowCode; req.rowCodeRc = T.rowCodeRc; req.padCode = T.rowCode[(uint8_t)'N']; req.rowsBound = rowsBound;
+	const auto t1 = std::chrono::steady_clock::now();
+	GaSeededPlan plan;
+	int status = GA_S_OK;
+	b->dev = g->device->beginSeededBatch(req, plan, &status);
+	if (!b->dev) return status ? status : GA_E_DEVICE;
+	const auto t2 = std::chrono::steady_clock::now();
+	// the host's records, copied from the download
+	const size_t nSlots = nReads * p.max_seeds;
+	b->seedOutN.assign(plan.outN, plan.outN + nReads * 3);
+	b->seedOut.assign(plan.outSeed, plan.outSeed + nSlots * 3);
+	if (byLocus) { b->seedOutLocus.assign(plan.outLocus, plan.outLocus + nSlots * 3); b->seedNLoci.assign(plan.outNLoci, plan.outNLoci + nReads); }
+	size_t nSeeds = 0;
+	for (size_t i = 0; i < nReads; i++)
+	{
+		const uint32_t n = std::min(plan.outN[i * 3], p.max_seeds);
+		b->reads[i].firstSeed = nSeeds;
+		b->reads[i].nSeeds = n;
+		nSeeds += n;
+	}
+	b->seeds.resize(nSeeds);
+	for (size_t i = 0; i < nReads; i++)
+		for (size_t t = 0; t < b->reads[i].nSeeds; t++)
+		{
+			const GaPlanSeed& ps = plan.seeds[i * p.max_seeds + t];
+			SeedPlan& sp = b->seeds[b->reads[i].firstSeed + t];
+			sp.valid = ps.valid != 0; sp.early = ps.early; sp.seedNodeIndex = ps.seed_node_index; sp.fwJob = ps.fw_job; sp.bwJob = ps.bw_job; sp.pos = ps.pos;
+		}
+	b->jobs.assign(plan.jobs, plan.jobs + plan.nJobs);
+	b->fills.resize(plan.nJobs);
+	for (size_t k = 0; k < plan.nJobs; k++)
+	{
+		const GaEqFill& f = plan.fills[k];
+		b->fills[k] = ga_batch::RowFill{plan.fillRead[k], b->jobs[k].rows_off, f.n, f.padded, f.pos, f.backward != 0};
+		b->cfg.max_rows = std::max(b->cfg.max_rows, b->jobs[k].n_rows);
+		b->cfg.max_slices = std::max(b->cfg.max_slices, b->jobs[k].n_rows / W);
+	}
+	b->rowsTotal = plan.rowsTotal;
+	b->eqWords = (plan.rowsTotal / W + 1) * 5;
+	b->readInvalid.reset(new std::atomic<uint8_t>[nReads + 1]);
+	for (size_t i = 0; i <= nReads; i++) b->readInvalid[i].store(0, std::memory_order_relaxed);
+	if (plan.badFills)
+	{
+		for (size_t k = 0; k < plan.nJobs; k++)
+			if (plan.badFills[k]) { b->anyInvalidRow.store(1, std::memory_order_relaxed); b->readInvalid[b->fills[k].read].store(1, std::memory_order_relaxed); }
+	}
+	else buildHostWords(b.get());
+	decideRuns(b.get());
+	b->seedMs = plan.seed_ms; b->planMs = plan.plan_ms; b->eqMs = plan.eq_ms;
+	plan.keep.reset();
+	const auto t3 = std::chrono::steady_clock::now();
+	ga_batch* bp = b.get();
+	status = b->dev->finishSeeded(b->jobs, b->cfg, [bp]() -> const std::vector<uint8_t>& { buildRows(bp); return bp->rows; }, b->eq.get(), b->eqWords);
+	if (status) return status;
+	b->cfg.emit_runs = b->dev->emittingRuns() ? 1u : 0u;
+	const auto t4 = std::chrono::steady_clock::now();
+	auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+	b->hostMs = ms(t0, t4) - (b->seedMs + b->planMs + b->eqMs);
+	if (getenv("GA_DEBUG_COLLECT"))
+		fprintf(stderr, "graphaligner_amd: seeded prepare: read copies %.1f ms, upload + seeds + plan + match words + download %.1f ms (kernels %.1f + %.1f + %.1f), host records %.1f ms, device batch %.1f ms\n",
+		        ms(t0, t1), ms(t1, t2), b->seedMs, b->planMs, b->eqMs, ms(t2, t3), ms(t3, t4));
+	*out = b.release();
+	return GA_S_OK;
+}
+
+int ga_align_reads(const ga_graph_t* g, const ga_read_t* reads, size_t nReads, const ga_seed_params_t* params, int byLocus,
+                   int initialBandwidth, int rampBandwidth, uint32_t flags, ga_results_t** out)
+{
+	ga_batch_t* b = nullptr;
+	int s = ga_batch_prepare_seeded(g, reads, nReads, params, byLocus, initialBandwidth, rampBandwidth, flags, &b);
+	if (s) return s;
+	s = ga_batch_run(b);
+	if (!s) s = ga_batch_collect(b, out);
+	ga_batch_free(b);
+	return s;
+}
+
+int ga_batch_prepare_stats(const ga_batch_t* b, ga_batch_prepare_stats_t* out)
+{
+	if (!b || !out || !b->seeded) return GA_E_INVALID;
+	memset(out, 0, sizeof(*out));
+	out->seed_kernel_ms = b->seedMs; out->plan_kernel_ms = b->planMs; out->eq_kernel_ms = b->eqMs; out->host_ms = b->hostMs;
+	out->n_seeds = b->seeds.size(); out->n_jobs = b->jobs.size();
+	for (const ReadPlan& r : b->reads) if (r.nSeeds == 0) out->reads_without_seed++;
+	return GA_S_OK;
+}
+
+int ga_batch_plan_copy(const ga_batch_t* b, uint64_t* job_rows_off, uint32_t* job_n_rows, uint32_t* job_seed_node, uint32_t* job_trace_rows, size_t job_capacity,
+                       uint64_t* seed_pos, uint32_t* seed_node_index, int32_t* seed_early, uint8_t* seed_valid, int64_t* seed_bw_job, int64_t* seed_fw_job, size_t seed_capacity,
+                       uint64_t* fill_read, uint64_t* fill_off, uint64_t* fill_n, uint64_t* fill_padded, uint64_t* fill_pos, uint8_t* fill_backward, size_t fill_capacity,
+                       size_t* counts)
+{
+	if (!b) return GA_E_INVALID;
+	if (counts) { counts[0] = b->jobs.size(); counts[1] = b->seeds.size(); counts[2] = b->fills.size(); }
+	for (size_t k = 0; k < std::min(job_capacity, b->jobs.size()); k++)
+	{
+		const GaJob& j = b->jobs[k];
+		if (job_rows_off) job_rows_off[k] = j.rows_off;
+		if (job_n_rows) job_n_rows[k] = j.n_rows;
+		if (job_seed_node) job_seed_node[k] = j.seed_node;
+		if (job_trace_rows) job_trace_rows[k] = j.trace_rows;
+	}
+	for (size_t k = 0; k < std::min(seed_capacity, b->seeds.size()); k++)
+	{
+		const SeedPlan& sp = b->seeds[k];
+		if (seed_pos) seed_pos[k] = sp.pos;
+		if (seed_node_index) seed_node_index[k] = sp.seedNodeIndex;
+		if (seed_early) seed_early[k] = sp.early;
+		if (seed_valid) seed_valid[k] = sp.valid ? 1 : 0;
+		if (seed_bw_job) seed_bw_job[k] = sp.bwJob;
+		if (seed_fw_job) seed_fw_job[k] = sp.fwJob;
+	}
+	for (size_t k = 0; k < std::min(fill_capacity, b->fills.size()); k++)
+	{
+		const ga_batch::RowFill& f = b->fills[k];
+		if (fill_read) fill_read[k] = f.read;
+		if (fill_off) fill_off[k] = f.off;
+		if (fill_n) fill_n[k] = f.n;
+		if (fill_padded) fill_padded[k] = f.padded;
+		if (fill_pos) fill_pos[k] = f.pos;
+		if (fill_backward) fill_backward[k] = f.backward ? 1 : 0;
+	}
+	return GA_S_OK;
+}
+
 int ga_batch_run(ga_batch_t* b)
 {
 	if (!b || !b->dev) return GA_E_INVALID;
@@ -942,6 +1176,18 @@ int ga_batch_run(ga_batch_t* b)
 	b->ran = s == GA_S_OK;
 	return s;
 }
+
+}  // extern "C"
+GaBatchSeedView ga_batch_seed_view(const ga_batch* b)
+{
+	GaBatchSeedView v;
+	if (!b || !b->seeded) return v;
+	v.seeded = true; v.byLocus = b->byLocus; v.g = b->g; v.nReads = b->reads.size(); v.maxSeeds = b->seedParams.max_seeds;
+	v.outN = b->seedOutN.data(); v.outSeed = b->seedOut.data(); v.outLocus = b->seedOutLocus.data(); v.outNLoci = b->seedNLoci.data();
+	v.kernel_ms = b->seedMs;
+	return v;
+}
+extern "C" {
 
 int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out)
 {

@@ -455,6 +455,57 @@ struct DevSeedEngine : GaSeedEngine
 	int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override { return run(seqs, lens, nReads, p, out, false); }
 	int findLoci(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override { return run(seqs, lens, nReads, p, out, true); }
 
+	// what every launch of the seeding kernels shares: the number of wave slots, the per-slot hit (and, by locus, label) buffers, grown
+	// when needed, and the launch record but for the reads and the outputs.  Under `lock`.
+	int prepareLaunch(gas::SeedLaunch& L, const GaSeedParams& p, size_t nReads, bool byLocus, uint32_t& slots)
+	{
+		// (the kernel waits on dependent loads: directory, keys, entry, coordinate; sixteen waves per CU hide them, and the kernel's
+		// registers and LDS would allow more)
+		slots = (uint32_t)std::min<size_t>(nReads, (size_t)std::max(cus, 1) * (byLocus ? kLociWavesPerCu : kWavesPerCu));
+		const size_t needHits = (size_t)slots * p.max_hits * 20;
+		if (needHits > hitsBytes)
+		{
+			if (hits) hipFree(hits);
+			hits = nullptr; hitsBytes = 0;
+			GAS_HIP_OK(hipMalloc(&hits, needHits));
+			hitsBytes = needHits;
+		}
+		const size_t needLoci = byLocus ? (size_t)slots * p.max_hits * 28 : 0;
+		if (needLoci > lociBytes)
+		{
+			if (loci) hipFree(loci);
+			loci = nullptr; lociBytes = 0;
+			GAS_HIP_OK(hipMalloc(&loci, needLoci));
+			lociBytes = needLoci;
+		}
+		memset(&L, 0, sizeof(L));
+		L.ix = ix; L.p = p;
+		L.n_reads = (uint32_t)nReads;
+		const size_t per = (size_t)slots * p.max_hits;
+		L.hit_dx = (int64_t*)hits; L.hit_p = (uint32_t*)((uint8_t*)hits + per * 8); L.hit_node = L.hit_p + per; L.hit_sup = L.hit_node + per;
+		if (byLocus) { L.loc_best = (uint64_t*)loci; L.loc_lab = (uint32_t*)((uint8_t*)loci + per * 8); L.loc_alt = L.loc_lab + per; L.loc_last = L.loc_alt + per; L.loc_run = L.loc_last + per; L.loc_nbr = L.loc_run + per; }
+		return 0;
+	}
+
+	// The seeding kernel over reads that lie in device memory already (a seeded batch, ga_plan.h), on the caller's stream; the outputs stay in
+	// device memory, where the caller's pointers say (cleared by the caller).  The caller holds `lock` from before this call until its
+	// stream has finished the kernel: the hit and label buffers are per graph.
+	int launchResident(const GaSeedParams& p, size_t nReads, bool byLocus, const uint8_t* seq, const gas::SeedRead* reads, const uint32_t* order,
+	                   uint32_t* outN, uint32_t* outSeed, uint32_t* outLocus, uint32_t* outNLoci, hipStream_t stream)
+	{
+		if (!have) return 100;
+		gas::SeedLaunch L;
+		uint32_t slots = 0;
+		if (int st = prepareLaunch(L, p, nReads, byLocus, slots)) return st;
+		L.seq = seq; L.reads = reads; L.order = order;
+		L.out_n = outN; L.out_seed = outSeed;
+		if (byLocus) { L.out_locus = outLocus; L.out_nloci = outNLoci; }
+		if (byLocus) hipLaunchKernelGGL(ga_seed_find_loci_kernel, dim3(slots), dim3(64), 0, stream, L);
+		else hipLaunchKernelGGL(ga_seed_find_kernel, dim3(slots), dim3(64), 0, stream, L);
+		GAS_HIP_OK(hipGetLastError());
+		return 0;
+	}
+
 	// byLocus: one seed per locus (ga_seed_find_loci_kernel) instead of hit by hit
 	int run(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out, bool byLocus)
 	{
@@ -500,42 +551,16 @@ struct DevSeedEngine : GaSeedEngine
 			GAS_HIP_OK(hipMalloc(&work, total + total / 8));
 			workBytes = total + total / 8;
 		}
-		// (the kernel waits on dependent loads: directory, keys, entry, coordinate; sixteen waves per CU hide them, and the kernel's
-		// registers and LDS would allow more)
-		const uint32_t slots = (uint32_t)std::min<size_t>(nReads, (size_t)std::max(cus, 1) * (byLocus ? kLociWavesPerCu : kWavesPerCu));
-		const size_t needHits = (size_t)slots * p.max_hits * 20;
-		if (needHits > hitsBytes)
-		{
-			if (hits) hipFree(hits);
-			hits = nullptr; hitsBytes = 0;
-			GAS_HIP_OK(hipMalloc(&hits, needHits));
-			hitsBytes = needHits;
-		}
-		const size_t needLoci = byLocus ? (size_t)slots * p.max_hits * 28 : 0;
-		if (needLoci > lociBytes)
-		{
-			if (loci) hipFree(loci);
-			loci = nullptr; lociBytes = 0;
-			GAS_HIP_OK(hipMalloc(&loci, needLoci));
-			lociBytes = needLoci;
-		}
+		gas::SeedLaunch L;
+		uint32_t slots = 0;
+		if (int st = prepareLaunch(L, p, nReads, byLocus, slots)) return st;
 		if (!evA) { GAS_HIP_OK(hipEventCreate(&evA)); GAS_HIP_OK(hipEventCreate(&evB)); }
 		uint8_t* w = (uint8_t*)work;
 		GAS_HIP_OK(hipMemcpyAsync(w, host.get(), oNext, hipMemcpyHostToDevice, 0));
 		GAS_HIP_OK(hipMemsetAsync(w + oNext, 0, total - oNext, 0));
-		gas::SeedLaunch L;
-		memset(&L, 0, sizeof(L));
-		L.ix = ix; L.p = p;
 		L.seq = w + oSeq; L.reads = (const gas::SeedRead*)(w + oRecs); L.order = (const uint32_t*)(w + oOrder);
-		L.n_reads = (uint32_t)nReads;
-		const size_t per = (size_t)slots * p.max_hits;
-		L.hit_dx = (int64_t*)hits; L.hit_p = (uint32_t*)((uint8_t*)hits + per * 8); L.hit_node = L.hit_p + per; L.hit_sup = L.hit_node + per;
 		L.out_n = (uint32_t*)(w + oOutN); L.out_seed = (uint32_t*)(w + oOutSeed);
-		if (byLocus)
-		{
-			L.loc_best = (uint64_t*)loci; L.loc_lab = (uint32_t*)((uint8_t*)loci + per * 8); L.loc_alt = L.loc_lab + per; L.loc_last = L.loc_alt + per; L.loc_run = L.loc_last + per; L.loc_nbr = L.loc_run + per;
-			L.out_locus = (uint32_t*)(w + oOutLocus); L.out_nloci = (uint32_t*)(w + oOutNLoci);
-		}
+		if (byLocus) { L.out_locus = (uint32_t*)(w + oOutLocus); L.out_nloci = (uint32_t*)(w + oOutNLoci); }
 		GAS_HIP_OK(hipEventRecord(evA, 0));
 		if (byLocus) hipLaunchKernelGGL(ga_seed_find_loci_kernel, dim3(slots), dim3(64), 0, 0, L);
 		else hipLaunchKernelGGL(ga_seed_find_kernel, dim3(slots), dim3(64), 0, 0, L);

@@ -148,23 +148,9 @@ int ga_graph_seed_index_copy(const ga_graph_t* g, uint64_t* keys, uint32_t* node
 	return e->copy(keys, node_indices, offsets, capacity);
 }
 
-// byLocus: ga_find_seeds_loci
-static int findSeeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out, bool byLocus)
+// the public set from the back end's per-slot arrays: node indices become (bigraph id, reverse)
+static ga_seed_set_t* makeSeedSet(const GaGraphView& v, const GaSeedOut& r, uint32_t max_seeds, size_t n_reads, bool byLocus)
 {
-	GaGraphView v;
-	GaSeedEngine* e = nullptr;
-	if (int s = engineOf(g, v, &e)) return s;
-	ga_seed_params_t p;
-	ga_seed_params_default(&p);
-	if (params) p = *params;
-	if (!out || (n_reads && !reads) || !paramsOk(p) || !e->built()) return GA_E_INVALID;
-	if (e->info().k != p.k || e->info().sample_shift != p.sample_shift) return GA_E_INVALID;
-	std::vector<const char*> seqs(n_reads);
-	std::vector<size_t> lens(n_reads);
-	for (size_t i = 0; i < n_reads; i++) { seqs[i] = reads[i].sequence; lens[i] = reads[i].length; if (lens[i] && !seqs[i]) return GA_E_INVALID; }
-	const GaSeedParams bp{p.k, p.sample_shift, p.max_occ, p.max_hits, p.window, p.diag_tol, p.min_support, p.max_seeds};
-	GaSeedOut r;
-	if (int s = byLocus ? e->findLoci(seqs.data(), lens.data(), n_reads, bp, r) : e->find(seqs.data(), lens.data(), n_reads, bp, r)) return s;
 	SeedSetOwner* o = new SeedSetOwner();
 	memset(&o->pub, 0, sizeof(o->pub));
 	o->offsets.assign(n_reads + 1, 0);
@@ -175,7 +161,7 @@ static int findSeeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads
 		o->truncated[i] = r.truncated[i] ? 1 : 0;
 		for (uint32_t t = 0; t < r.n_seeds[i]; t++)
 		{
-			const size_t at = i * p.max_seeds + t;
+			const size_t at = i * max_seeds + t;
 			const int64_t id = (*v.ids)[r.node[at]];
 			ga_seed_t sd;
 			memset(&sd, 0, sizeof(sd));
@@ -196,7 +182,28 @@ static int findSeeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads
 		o->locusHits.reserve(1); o->locusFirstP.reserve(1); o->locusLastP.reserve(1); o->nLoci.reserve(1);
 		o->pub.locus_hits = o->locusHits.data(); o->pub.locus_first_p = o->locusFirstP.data(); o->pub.locus_last_p = o->locusLastP.data(); o->pub.n_loci = o->nLoci.data();
 	}
-	*out = &o->pub;
+	return &o->pub;
+}
+
+
+// byLocus: ga_find_seeds_loci
+static int findSeeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out, bool byLocus)
+{
+	GaGraphView v;
+	GaSeedEngine* e = nullptr;
+	if (int s = engineOf(g, v, &e)) return s;
+	ga_seed_params_t p;
+	ga_seed_params_default(&p);
+	if (params) p = *params;
+	if (!out || (n_reads && !reads) || !paramsOk(p) || !e->built()) return GA_E_INVALID;
+	if (e->info().k != p.k || e->info().sample_shift != p.sample_shift) return GA_E_INVALID;
+	std::vector<const char*> seqs(n_reads);
+	std::vector<size_t> lens(n_reads);
+	for (size_t i = 0; i < n_reads; i++) { seqs[i] = reads[i].sequence; lens[i] = reads[i].length; if (lens[i] && !seqs[i]) return GA_E_INVALID; }
+	const GaSeedParams bp{p.k, p.sample_shift, p.max_occ, p.max_hits, p.window, p.diag_tol, p.min_support, p.max_seeds};
+	GaSeedOut r;
+	if (int s = byLocus ? e->findLoci(seqs.data(), lens.data(), n_reads, bp, r) : e->find(seqs.data(), lens.data(), n_reads, bp, r)) return s;
+	*out = makeSeedSet(v, r, p.max_seeds, n_reads, byLocus);
 	return GA_S_OK;
 }
 
@@ -208,6 +215,30 @@ int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, c
 int ga_find_seeds_loci(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out)
 {
 	return findSeeds(g, reads, n_reads, params, out, true);
+}
+
+// the seeds a batch of ga_batch_prepare_seeded was planned from, in the shape ga_find_seeds / ga_find_seeds_loci return them
+int ga_batch_seeds(const ga_batch_t* b, ga_seed_set_t** out)
+{
+	if (!b || !out) return GA_E_INVALID;
+	const GaBatchSeedView bv = ga_batch_seed_view(b);
+	if (!bv.seeded) return GA_E_INVALID;
+	const GaGraphView v = ga_graph_view(bv.g);
+	const size_t n = bv.nReads, slots = n * bv.maxSeeds;
+	GaSeedOut r;
+	r.n_seeds.resize(n); r.n_hits.resize(n); r.truncated.resize(n);
+	r.node.resize(slots); r.pos.resize(slots); r.support.resize(slots);
+	for (size_t i = 0; i < n; i++) { r.n_seeds[i] = bv.outN[i * 3]; r.n_hits[i] = bv.outN[i * 3 + 1]; r.truncated[i] = bv.outN[i * 3 + 2]; }
+	for (size_t i = 0; i < slots; i++) { r.node[i] = bv.outSeed[i * 3]; r.pos[i] = bv.outSeed[i * 3 + 1]; r.support[i] = bv.outSeed[i * 3 + 2]; }
+	if (bv.byLocus)
+	{
+		r.locus_hits.resize(slots); r.locus_first_p.resize(slots); r.locus_last_p.resize(slots);
+		for (size_t i = 0; i < slots; i++) { r.locus_hits[i] = bv.outLocus[i * 3]; r.locus_first_p[i] = bv.outLocus[i * 3 + 1]; r.locus_last_p[i] = bv.outLocus[i * 3 + 2]; }
+		r.n_loci.assign(bv.outNLoci, bv.outNLoci + n);
+	}
+	r.kernel_ms = bv.kernel_ms;
+	*out = makeSeedSet(v, r, bv.maxSeeds, n, bv.byLocus);
+	return GA_S_OK;
 }
 
 void ga_seed_set_free(ga_seed_set_t* s)

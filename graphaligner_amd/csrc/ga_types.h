@@ -96,6 +96,10 @@ struct GaLaunch {
 	uint32_t reserved;
 };
 
+// what the plan kernels (ga_plan.h) leave per seed slot: the seed as ga_batch_prepare plans it (early = a ga_status fixed before any device
+// work; job numbers, -1: none)
+struct GaPlanSeed { uint32_t pos, seed_node_index; int32_t early; uint32_t valid; int32_t bw_job, fw_job; };
+
 // seeding parameters (include/graphaligner_amd.h: ga_seed_params_t, same fields in the same order)
 struct GaSeedParams { uint32_t k, sample_shift, max_occ, max_hits, window, diag_tol, min_support, max_seeds; };
 

@@ -14,14 +14,31 @@ def shard_indices(lengths, rank, world):
     return [int(i) for i in order[rank::world]]
 
 
-def align_sharded(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None):
+def _seeding(seeds, find_seeds):
+    """seeds=None asks for seeded batches (Graph.prepare_seeded): find_seeds = dict(params=..., loci=...) says how, {} for the defaults"""
+    if seeds is not None:
+        return None
+    if find_seeds is None:
+        raise ValueError("seeds=None needs find_seeds=dict(params=..., loci=...)")
+    return dict(params=find_seeds.get("params"), loci=bool(find_seeds.get("loci", False)))
+
+
+def align_sharded(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, find_seeds=None):
     """every rank calls this with the SAME reads/seeds and its own `graph` (already uploaded to its
-    GPU); rank 0 gets the full result list in input order, other ranks get None"""
+    GPU); rank 0 gets the full result list in input order, other ranks get None.  seeds=None with
+    find_seeds=dict(params=..., loci=...): the seeds are found on the device (Graph.align_reads)"""
+    how = _seeding(seeds, find_seeds)
+
+    def align(rd, sd):
+        if how is not None:
+            return graph.align_reads(rd, how["params"], how["loci"], bandwidth, ramp, flags)
+        return graph.align(rd, sd, bandwidth, ramp, flags)
+
     if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-        return graph.align(reads, seeds, bandwidth, ramp, flags)
+        return align(reads, seeds)
     rank, world = dist.get_rank(), dist.get_world_size()
     mine = shard_indices([len(r) for r in reads], rank, world)
-    local = graph.align([reads[i] for i in mine], [seeds[i] for i in mine], bandwidth, ramp, flags) if mine else []
+    local = align([reads[i] for i in mine], None if how is not None else [seeds[i] for i in mine]) if mine else []
     gathered = [None] * world
     dist.all_gather_object(gathered, (mine, local))
     if rank != 0:
@@ -65,10 +82,12 @@ class _Counter:
         return int(self.store.add(self.key, 1)) - 1
 
 
-def run_overlapped(graph, inputs, bandwidth, ramp=0, flags=0, summary=False, gam=False):
+def run_overlapped(graph, inputs, bandwidth, ramp=0, flags=0, summary=False, gam=False, find_seeds=None):
     """`inputs` yields (key, (reads, seeds)) or (key, binding.ReadSet); three stages overlap on separate host threads and HIP streams:
     job building + upload of input k+1, the kernels of input k, download + assembly of input k-1.  Returns [(key, results)]; results
-    are Python lists, per-read record arrays (summary=True) or the bytes of one GAM group per input (gam=True)."""
+    are Python lists, per-read record arrays (summary=True) or the bytes of one GAM group per input (gam=True).
+    find_seeds=dict(params=..., loci=...): an input whose seeds are None, and every ReadSet, becomes a seeded batch
+    (Graph.prepare_seeded): seeding is then the first part of the stage in front of the kernels."""
     from concurrent.futures import ThreadPoolExecutor
     it = iter(inputs)
 
@@ -78,7 +97,13 @@ def run_overlapped(graph, inputs, bandwidth, ramp=0, flags=0, summary=False, gam
         except StopIteration:
             return None
         if isinstance(what, tuple):
+            if what[1] is None:
+                how = _seeding(None, find_seeds)
+                return key, graph.prepare_seeded(what[0], how["params"], how["loci"], bandwidth, ramp, flags)
             return key, graph.prepare(what[0], what[1], bandwidth, ramp, flags)
+        if find_seeds is not None:
+            how = _seeding(None, find_seeds)
+            return key, graph.prepare_seeded(what, how["params"], how["loci"], bandwidth, ramp, flags)
         return key, graph.prepare(what, None, bandwidth, ramp, flags)
 
     def finish(batch):
@@ -102,7 +127,8 @@ def run_overlapped(graph, inputs, bandwidth, ramp=0, flags=0, summary=False, gam
         return [(k, f.result()) for k, f in done]
 
 
-def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chunk_reads=65536, tag="ga_queue", summary=False, gam=False, names=None):
+def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chunk_reads=65536, tag="ga_queue", summary=False, gam=False, names=None,
+                 find_seeds=None):
     """every rank calls this with the SAME reads/seeds and its own `graph` (already uploaded to its GPU).  Chunks of reads are pulled
     from a shared counter, so a rank that finishes early takes more; on each rank the stages of consecutive chunks overlap
     (run_overlapped).  Rank 0 gets the full result in input order, other ranks get None.  No collective on the data path; what travels
@@ -110,7 +136,9 @@ def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chu
       summary=True  a numpy record array (Batch.collect(summary=True)), merged into one array in input order;
       gam=True      the bytes of a GAM group (ga_results_encode_gam): rank 0 returns them joined in chunk order -- GAM groups
                     concatenate (stream.hpp:24-63), so that is the GAM file of the whole read set, reads ordered longest first;
-      otherwise     Python lists of per-read dicts (tests and small inputs: pickling 200 000 of those is not a transport)."""
+      otherwise     Python lists of per-read dicts (tests and small inputs: pickling 200 000 of those is not a transport).
+    seeds=None with find_seeds=dict(params=..., loci=...): every chunk is a seeded batch (Graph.prepare_seeded)."""
+    how = _seeding(seeds, find_seeds)
     chunks = make_chunks([len(r) for r in reads], chunk_reads)
     counter = _Counter(dist, tag)
     multi = counter.store is not None
@@ -123,11 +151,11 @@ def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chu
             idx = chunks[k]
             if gam and names is not None:
                 from . import binding
-                yield k, binding.ReadSet([reads[i] for i in idx], [seeds[i] for i in idx], [names[i] for i in idx])
+                yield k, binding.ReadSet([reads[i] for i in idx], [[] if how is not None else seeds[i] for i in idx], [names[i] for i in idx])
             else:
-                yield k, ([reads[i] for i in idx], [seeds[i] for i in idx])
+                yield k, ([reads[i] for i in idx], None if how is not None else [seeds[i] for i in idx])
 
-    mine = run_overlapped(graph, taken(), bandwidth, ramp, flags, summary, gam)
+    mine = run_overlapped(graph, taken(), bandwidth, ramp, flags, summary, gam, how)
     if multi:
         gathered = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
         dist.gather_object(mine, gathered, dst=0)

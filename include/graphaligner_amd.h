@@ -348,6 +348,45 @@ int ga_find_seeds(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, c
 int ga_find_seeds_loci(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, ga_seed_set_t** out);
 void ga_seed_set_free(ga_seed_set_t* s);
 
+/* ---- seeded batches: seeds found and jobs planned on the device, in one call ------------------------------ */
+/* ga_batch_prepare_seeded = ga_find_seeds (by_locus != 0: ga_find_seeds_loci) followed by ga_batch_prepare on those seeds, with one upload
+ * of the reads and the seeds and the job plan made in HBM.  The batch runs, collects, reports and is freed like
+ * one of ga_batch_prepare, and gives the same results.  THE PLAN RULE, on node indices.  Per read of length L, its seeds in the seeder's
+ * order; a seed has hit node n and read position p.  twin(n): the node whose digraph id is n's ^ 1, or none.  reverse = id(n) & 1;
+ * seedNodeIndex = reverse ? twin(n) : n (the even-id node of the pair); fwNode = n, bwNode = twin(n).  Checks, in this order: no twin:
+ * GA_S_BAD_SEED; !(p < L): GA_S_ASSERTION; len(fwNode) != len(bwNode): GA_S_ASSERTION.  Backward part when p > 0, with ovl the graph's
+ * dbg_overlap: L < p + ovl, or a character of seq[0 .. p + ovl) that has no complement (CommonUtils.cpp:60-136): GA_S_ASSERTION, the seed
+ * is not valid and gets no jobs; else a job of n = p + ovl rows, n_rows = n rounded up to 64, seed_node = bwNode, trace_rows = p.
+ * Forward part when p < L - 1: n = L - p rows, n_rows likewise, seed_node = fwNode, trace_rows = n >= ovl ? n - ovl : 0.  rows_off is the
+ * running 64-bit sum of n_rows in the order (read, seed, backward before forward).  A read without a seed has no jobs and collects as
+ * GA_S_ASSERTION, as with an empty seed list given to ga_batch_prepare.
+ * Errors: GA_E_INVALID without a seed index, with params->k / sample_shift other than the index's, and on a back end without the feature.
+ * Memory kept with the graph from the first call on: the twin table, 5 bytes per node. */
+int ga_batch_prepare_seeded(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params /* NULL: defaults */, int by_locus,
+                            int initial_bandwidth, int ramp_bandwidth, uint32_t flags, ga_batch_t** out);
+/* ga_batch_prepare_seeded + ga_batch_run + ga_batch_collect */
+int ga_align_reads(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_params_t* params, int by_locus,
+                   int initial_bandwidth, int ramp_bandwidth, uint32_t flags, ga_results_t** out);
+/* the seeds the batch was planned from: the set ga_find_seeds / ga_find_seeds_loci would have returned (free with ga_seed_set_free);
+ * GA_E_INVALID for a batch of ga_batch_prepare */
+int ga_batch_seeds(const ga_batch_t* b, ga_seed_set_t** out);
+/* the plan of ANY batch, for tests and tools: the first min(count, capacity) entries of each kind; a null array is skipped; counts (may
+ * be null) receives the numbers of jobs, seeds and fills.  Jobs and fills are in plan order and correspond one to one; a seed's job
+ * numbers are -1 where it has no such job; seeds are all reads' seeds in order. */
+int ga_batch_plan_copy(const ga_batch_t* b, uint64_t* job_rows_off, uint32_t* job_n_rows, uint32_t* job_seed_node, uint32_t* job_trace_rows, size_t job_capacity,
+                       uint64_t* seed_pos, uint32_t* seed_node_index, int32_t* seed_early, uint8_t* seed_valid, int64_t* seed_bw_job, int64_t* seed_fw_job, size_t seed_capacity,
+                       uint64_t* fill_read, uint64_t* fill_off, uint64_t* fill_n, uint64_t* fill_padded, uint64_t* fill_pos, uint8_t* fill_backward, size_t fill_capacity,
+                       size_t* counts);
+typedef struct ga_batch_prepare_stats {
+	double seed_kernel_ms;       /* HIP-event time of the seeding kernel */
+	double plan_kernel_ms;       /* ... of the plan kernels and their scans */
+	double eq_kernel_ms;         /* ... of the read-coding (match word) kernel */
+	double host_ms;              /* wall time of the call less the three above */
+	uint64_t n_seeds, n_jobs, reads_without_seed;
+} ga_batch_prepare_stats_t;
+/* GA_E_INVALID for a batch of ga_batch_prepare */
+int ga_batch_prepare_stats(const ga_batch_t* b, ga_batch_prepare_stats_t* out);
+
 /* ---- file formats either side of the path (no libprotobuf; zlib only) --------------------------------- */
 /* gzip-framed vg.Graph chunks (stream.hpp:24-118) -> graph, as DirectedGraph::StreamVGGraphFromFile
  * (BigraphToDigraph.cpp:106-135): all nodes first, then all edges, then Finalize; DBGOverlap stays 0 */

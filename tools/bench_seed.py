@@ -25,6 +25,12 @@ index, the coordinate switched before every timed call so that the two alternate
 time next to the index build's, its rounds, and under either coordinate the ga_find_seeds_loci kernel time, seeds, jobs and the
 aligner's kernel_ms from those seeds.  --shuffle-nodes: the graph's nodes in a random order (random.Random(1).shuffle), edges as they
 are: the file that is not in path order.
+
+--seeded: seeded batches (ga_batch_prepare_seeded) measured beside the two-call path on the same reads and index, at the C ABI (no
+Python lists in between): wall time of ga_find_seeds_loci + ga_batch_prepare against wall time of ga_batch_prepare_seeded, alternating
+call by call (--warmup calls, then --calls timed ones, at least 10), with the seeded call's split (ga_batch_prepare_stats_t); then
+the host-to-host rate of sharding.run_overlapped over 12 chunks of the reads, the stage in front of the kernels being the two calls
+or the one, alternating run by run.  The row says whether either difference exceeds the larger of the two min-max spreads.
 """
 import argparse
 import json
@@ -34,6 +40,97 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def seeded_row(args, G, reads, gen_s):
+    """--seeded: see the module's text"""
+    import ctypes as C
+    import numpy as np
+    from graphaligner_amd import binding, sharding
+    L = G.L
+    st = G.build_seed_index()
+    p = G._seed_params(None, "bench_seed")
+    rs = binding.ReadSet(reads, [[]] * len(reads))
+    n = rs.n_reads
+
+    def two_call(r=rs):
+        """ga_find_seeds_loci, then ga_batch_prepare on the set's own arrays; returns (the batch, wall ms, the set's kernel ms)"""
+        t0 = time.perf_counter()
+        out = C.POINTER(binding.GaSeedSetLoci)()
+        binding._check(L, L.ga_find_seeds_loci(G.h, r.arr, r.n_reads, C.byref(p), C.byref(out)), "ga_find_seeds_loci")
+        S = out.contents
+        shim = binding.ReadSet.__new__(binding.ReadSet)
+        shim._keep, shim._names, shim.arr, shim.sarr, shim.n_reads, shim.total_bp = r._keep, r._names, r.arr, S.seeds, r.n_reads, r.total_bp
+        shim.offs = np.ctypeslib.as_array(S.seed_offsets, shape=(r.n_reads + 1,))
+        b = binding.Batch(G, shim, None, args.bandwidth, 0, 0)
+        ms = (time.perf_counter() - t0) * 1e3
+        kernel_ms = S.kernel_ms
+        b._rs = r
+        L.ga_seed_set_free(out)
+        return b, ms, kernel_ms
+
+    def one_call(r=rs):
+        t0 = time.perf_counter()
+        b = G.prepare_seeded(r, None, True, args.bandwidth)
+        return b, (time.perf_counter() - t0) * 1e3
+
+    calls = max(args.calls, 10)
+    two_ms, two_kernel, one_ms, split = [], [], [], []
+    jobs = [0, 0]
+    for i in range(args.warmup + calls):
+        b, ms, kms = two_call()
+        jobs[0] = b.stats()["n_jobs"]
+        b.close()
+        b2, ms2 = one_call()
+        ps = b2.prepare_stats()
+        jobs[1] = ps["n_jobs"]
+        b2.close()
+        if i >= args.warmup:
+            two_ms.append(ms); two_kernel.append(kms); one_ms.append(ms2); split.append(ps)
+    two_ms, one_ms = np.array(two_ms), np.array(one_ms)
+
+    def stat(a, warmup=None):
+        return {"median": round(float(np.median(a)), 3), "min": round(float(a.min()), 3), "max": round(float(a.max()), 3), "calls": len(a),
+                "warmup": args.warmup if warmup is None else warmup}
+
+    def verdict(slow, fast):
+        """is `fast` shorter than `slow` by more than the larger of the two min-max spreads (medians)"""
+        spread = max(float(slow.max() - slow.min()), float(fast.max() - fast.min()))
+        gain = float(np.median(slow) - np.median(fast))
+        return {"difference": round(gain, 3), "larger_spread": round(spread, 3), "shorter_by_more_than_the_spread": bool(gain > spread)}
+
+    # the overlapped pipeline over 12 chunks, the stage in front of the kernels being the two calls or the one
+    chunk = (n + 11) // 12
+    sets = [binding.ReadSet(reads[a:a + chunk], [[]] * len(reads[a:a + chunk])) for a in range(0, n, chunk)]
+
+    class TwoCallGraph:
+        def prepare(self, what, seeds, bw, ramp, flags):
+            return two_call(what)[0]
+
+    bp = sum(len(r) for r in reads)
+    rate = {"two_call": [], "seeded": []}
+    aligned = {}
+    for i in range(1 + args.overlap_runs):
+        for kind in ("two_call", "seeded"):
+            t0 = time.perf_counter()
+            if kind == "two_call":
+                res = sharding.run_overlapped(TwoCallGraph(), list(enumerate(sets)), args.bandwidth, summary=True)
+            else:
+                res = sharding.run_overlapped(G, list(enumerate(sets)), args.bandwidth, summary=True, find_seeds=dict(params=None, loci=True))
+            s = time.perf_counter() - t0
+            aligned[kind] = int(sum(int(((r["status"] == 0) & (r["failed"] == 0)).sum()) for _, r in res))
+            if i:
+                rate[kind].append(s * 1e3)
+    wall = {k: np.array(v) for k, v in rate.items()}
+    return {
+        "tool": "tools/bench_seed.py --seeded", "graph": args.graph, "genome_bp": args.genome, "node_len": args.node_len, "reads": n, "read_len": args.read_len,
+        "read_bp": bp, "gen_s": round(gen_s, 1), "index_entries": st["entries"], "jobs": {"two_call": int(jobs[0]), "seeded": int(jobs[1])},
+        "prepare_wall_ms": {"two_call": stat(two_ms), "seeded": stat(one_ms), "two_call_seed_kernel_ms": round(float(np.median(two_kernel)), 3), **verdict(two_ms, one_ms)},
+        "seeded_split_ms": {k: round(float(np.median([d[k] for d in split])), 3) for k in ("seed_kernel_ms", "plan_kernel_ms", "eq_kernel_ms", "host_ms")},
+        "reads_without_seed": int(split[-1]["reads_without_seed"]),
+        "overlapped_12_chunks": {"wall_ms": {k: stat(v, 1) for k, v in wall.items()}, "Mbp_s": {k: round(bp / float(np.median(v)) / 1e3, 1) for k, v in wall.items()},
+                                 "reads_aligned": aligned, **verdict(wall["two_call"], wall["seeded"])},
+    }
 
 
 def main():
@@ -51,6 +148,8 @@ def main():
     ap.add_argument("--loci", action="store_true", help="also measure ga_find_seeds_loci (one seed per locus)")
     ap.add_argument("--coord", choices=["file", "topology"], default="file", help="topology: also measure the topology coordinate")
     ap.add_argument("--shuffle-nodes", action="store_true", help="node list in a random order")
+    ap.add_argument("--seeded", action="store_true", help="measure ga_batch_prepare_seeded beside ga_find_seeds_loci + ga_batch_prepare, and nothing else")
+    ap.add_argument("--overlap-runs", type=int, default=3, help="--seeded: timed run_overlapped passes per path (one warm-up pass each before them)")
     args = ap.parse_args()
     if args.node_len < 8 or not 0 <= args.max_walks <= 256:
         raise SystemExit("bench_seed.py: --node-len must be 8 or more and --max-walks 0..256")
@@ -75,6 +174,10 @@ def main():
         import random
         random.Random(1).shuffle(g.nodes)                       # (after the reads: they do not depend on the order)
     G = binding.Graph(gfa=g.gfa())
+
+    if args.seeded:
+        print(json.dumps(seeded_row(args, G, reads, gen_s)))
+        return
 
     grouped = {}
 
