@@ -145,6 +145,7 @@ class AlignerParams:
         self.seedWalks = 0          # --seed-walks: 0 = the in-node index, 1..256 = the walk index with that max_walks
         self.seedLoci = False       # --seed-loci: one seed per locus
         self.seedCoord = "file"     # --seed-coord: "file" or "topology"
+        self.opsFile = ""           # --ops-out: per aligned read its operations (GA_F_OPS): counts, identity and the run string
 
 
 def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr, seed_lib_path=None):
@@ -156,6 +157,8 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
         raise SystemExit(0)
     reads = load_reads(params.fastqFile)
     out.write("%d reads\n" % len(reads))
+    # (GA_F_OPS only when its file is asked for: the other output is the same with and without it)
+    flags = binding.GA_F_TRACE | (binding.GA_F_OPS if getattr(params, "opsFile", "") else 0)
     find_seeds = getattr(params, "findSeeds", False)
     if params.seedFile == "" and not find_seeds:
         err.write("either initial full band or seed file must be set\n")
@@ -190,7 +193,7 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
         if seeder is graph:
             try:
                 seeded = graph.prepare_seeded([r.sequence for r in reads[::-1]], dict(max_seeds=params.seedMax), by_locus,
-                                              params.initialBandwidth, params.rampBandwidth, flags=binding.GA_F_TRACE)
+                                              params.initialBandwidth, params.rampBandwidth, flags=flags)
             except binding.SeededUnsupported:
                 seeded = None
         if seeded is not None:
@@ -219,7 +222,7 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
             seeded.close()
     elif with_seeds:
         batch = graph.prepare([reads[i].sequence for i in with_seeds], [seeds_of[i] for i in with_seeds],
-                              params.initialBandwidth, params.rampBandwidth, flags=binding.GA_F_TRACE)
+                              params.initialBandwidth, params.rampBandwidth, flags=flags)
         batch.run()
         for i, r in zip(with_seeds, batch.collect()):
             results[i] = r
@@ -272,6 +275,14 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
     if params.alignmentFile != "":
         with open(params.alignmentFile, "wb") as f:
             f.write(gam_group([encode_alignment(rd.seq_id, rd.sequence, r) for rd, r in written]))
+    if getattr(params, "opsFile", ""):
+        # per aligned read, in output order: name, matches, mismatches, insertions, deletions, identity = matches / all cells, the runs
+        with open(params.opsFile, "w") as f:
+            for rd, r in written:
+                c = r["op_counts"]
+                cells = c["match"] + c["mismatch"] + c["insertion"] + c["deletion"]
+                f.write("%s\t%d\t%d\t%d\t%d\t%.6f\t%s\n" % (rd.seq_id, c["match"], c["mismatch"], c["insertion"], c["deletion"],
+                                                             c["match"] / cells if cells else 0.0, binding.ops_string(r["ops"])))
     return [(rd.seq_id, r) for rd, r in written]
 
 
@@ -280,7 +291,7 @@ def parse_args(argv, err=sys.stderr):
     p = AlignerParams()
     initial_full_band = False
     coord_given = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord="])
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out="])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -315,6 +326,8 @@ def parse_args(argv, err=sys.stderr):
         elif o == "--seed-coord":
             p.seedCoord = a
             coord_given = True
+        elif o == "--ops-out":
+            p.opsFile = a
 
     def stop(msg):
         err.write(msg + "\n")

@@ -15,6 +15,8 @@ PRODUCT_SO = os.path.join(HERE, "libgraphaligner_amd.so")
 STATUS = {0: "OK", 1: "ASSERTION", 2: "UNSUPPORTED_BAND", 3: "BAD_SEED", 10: "CAPACITY", 20: "UNSUPPORTED_CYCLE", 21: "UNSUPPORTED_RAMP",
           100: "E_INVALID", 101: "E_NO_DEVICE", 102: "E_DEVICE", 103: "E_NOT_FINALIZED"}
 GA_F_TRACE = 1
+GA_F_OPS = 2
+OP_CODES = {1: "=", 2: "X", 3: "I", 4: "D", 5: "|"}
 GA_S_OK = 0
 GA_S_ASSERTION = 1
 
@@ -47,6 +49,22 @@ class GaReadResult(C.Structure):
 class GaResults(C.Structure):
     _fields_ = [("n_reads", C.c_size_t), ("reads", C.POINTER(GaReadResult)), ("n_mappings", C.c_size_t), ("mappings", C.POINTER(GaMapping)),
                 ("n_edit_bytes", C.c_size_t), ("edit_bytes", C.POINTER(C.c_char)), ("n_trace", C.c_size_t), ("trace", C.POINTER(GaTraceItem))]
+
+
+class GaReadOps(C.Structure):
+    _fields_ = [("first_op", C.c_uint64), ("n_ops", C.c_uint32), ("n_match", C.c_uint32), ("n_mismatch", C.c_uint32), ("n_insertion", C.c_uint32),
+                ("n_deletion", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GaResultsOps(C.Structure):
+    """ga_results_t with the three fields GA_F_OPS fills at its end.  Results of batches without the flag are read through GaResults
+    alone, so that a library from before those fields (bench.py --lib) is never read past its own struct."""
+    _fields_ = GaResults._fields_ + [("read_ops", C.POINTER(GaReadOps)), ("n_ops", C.c_size_t), ("ops", C.POINTER(C.c_uint32))]
+
+
+class GaBatchOpsStats(C.Structure):
+    _fields_ = [("count_kernel_ms", C.c_double), ("write_kernel_ms", C.c_double), ("jobs_coded", C.c_uint64), ("moves_read", C.c_uint64),
+                ("runs_written", C.c_uint64), ("reads_from_device", C.c_uint64), ("reads_from_host", C.c_uint64)]
 
 
 class GaBatchStats(C.Structure):
@@ -152,6 +170,8 @@ def load(path=None):
     L.ga_status_string.argtypes = [C.c_int]
     L.ga_status_string.restype = C.c_char_p
     L.ga_version.restype = C.c_char_p
+    if hasattr(L, "ga_batch_ops_stats"):                                   # (bench.py --lib may name a build from before GA_F_OPS)
+        L.ga_batch_ops_stats.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "ga_find_seeds"):
         L.ga_seed_params_default.argtypes = [C.c_void_p]
         L.ga_seed_params_default.restype = None
@@ -423,6 +443,7 @@ class Batch:
         self.g = graph
         L = self.L = graph.L
         self.loci = None                   # a seeded batch: whether its seeds are per locus
+        self.flags = int(flags)
         rs = reads if isinstance(reads, ReadSet) else ReadSet(reads, seeds if find_seeds is None else [[]] * len(reads), names)
         self._rs = rs                      # (the arrays must outlive the batch: GAM encoding reads the names)
         self._arr, self._sarr, self._offs = rs.arr, rs.sarr, rs.offs
@@ -452,6 +473,15 @@ class Batch:
         d = {k: getattr(st, k) for k, _ in st._fields_}
         d["stamps"] = list(st.stamps)
         return d
+
+    def ops_stats(self):
+        """ga_batch_ops_stats_t of a batch prepared with GA_F_OPS as a dict: the two kernels' times, jobs coded, moves read, runs written
+        and, from the last collect, how many reads got their runs from the device and from the host"""
+        if not hasattr(self.L, "ga_batch_ops_stats"):
+            raise RuntimeError("this library has no ga_batch_ops_stats")
+        st = GaBatchOpsStats()
+        _check(self.L, self.L.ga_batch_ops_stats(self.h, C.byref(st)), "ga_batch_ops_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     def seeds(self):
         """the SeedResult a seeded batch was planned from (what Graph.find_seeds would have returned); an error for other batches"""
@@ -505,11 +535,14 @@ class Batch:
 
     def collect(self, summary=False, unsplit=False):
         """summary=True: per-read numpy record array only (status, failed, score, n_mappings, ...), no Python lists;
-        unsplit=True: results of a graph loaded with split=... on the nodes of the GFA file (ga_results_unsplit)"""
-        out = C.POINTER(GaResults)()
+        unsplit=True: results of a graph loaded with split=... on the nodes of the GFA file (ga_results_unsplit).  A batch prepared
+        with GA_F_OPS: every read's dict also has ops (uint32 array of shape (n, 2): type, length) and op_counts (dict of the four
+        summed lengths); with summary=True the return value is (records, op_counts array of shape (reads, 4), list of ops arrays)"""
+        want_ops = bool(self.flags & GA_F_OPS)
+        out = C.POINTER(GaResultsOps if want_ops else GaResults)()
         _check(self.L, self.L.ga_batch_collect(self.h, C.byref(out)), "ga_batch_collect")
         if unsplit:
-            merged = C.POINTER(GaResults)()
+            merged = C.POINTER(GaResultsOps if want_ops else GaResults)()
             try:
                 _check(self.L, self.L.ga_results_unsplit(self.g.h, out, C.byref(merged)), "ga_results_unsplit")
             finally:
@@ -523,8 +556,18 @@ class Batch:
                                ("first_trace", "<u8"), ("n_trace", "<u8"), ("column_updates", "<u8")])
                 assert dt.itemsize == C.sizeof(GaReadResult)
                 buf = C.string_at(R.reads, R.n_reads * dt.itemsize) if R.n_reads else b""
-                return np.frombuffer(buf, dtype=dt).copy()
-            return _unpack(out.contents)
+                recs = np.frombuffer(buf, dtype=dt).copy()
+                if not want_ops:
+                    return recs
+                counts, runs = _unpack_ops(R)
+                return recs, counts, runs
+            reads = _unpack(out.contents)
+            if want_ops:
+                counts, runs = _unpack_ops(out.contents)
+                for i, r in enumerate(reads):
+                    r["ops"] = runs[i]
+                    r["op_counts"] = dict(match=int(counts[i, 0]), mismatch=int(counts[i, 1]), insertion=int(counts[i, 2]), deletion=int(counts[i, 3]))
+            return reads
         finally:
             self.L.ga_results_free(out)
 
@@ -553,6 +596,25 @@ def decode_seed_gam(data, lib_path=None):
     out = [(arr[i].read_name.decode(), (arr[i].seed.node_id, arr[i].seed.read_pos, bool(arr[i].seed.reverse))) for i in range(n.value)]
     L.ga_bytes_free(arr)
     return out
+
+
+def _unpack_ops(R):
+    """(counts of shape (reads, 4): match, mismatch, insertion, deletion; per read its runs as a uint32 array of shape (n, 2): type, length)"""
+    n = R.n_reads
+    counts = np.zeros((n, 4), dtype=np.int64)
+    runs = []
+    words = np.ctypeslib.as_array(R.ops, shape=(R.n_ops,)) if R.n_ops else np.zeros(0, dtype=np.uint32)
+    for i in range(n):
+        ro = R.read_ops[i]
+        counts[i] = (ro.n_match, ro.n_mismatch, ro.n_insertion, ro.n_deletion)
+        w = np.array(words[ro.first_op:ro.first_op + ro.n_ops], dtype=np.uint32)
+        runs.append(np.stack([w & 7, w >> 3], axis=1).astype(np.uint32) if len(w) else np.zeros((0, 2), dtype=np.uint32))
+    return counts, runs
+
+
+def ops_string(ops):
+    """runs (type, length) as a string such as 254=1X3I2D, with | for the split between the backward and the forward part"""
+    return "".join("|" if int(t) == 5 else "%d%s" % (int(n), OP_CODES[int(t)]) for t, n in ops)
 
 
 def _unpack(R):

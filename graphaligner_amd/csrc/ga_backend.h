@@ -53,6 +53,7 @@ struct GaRunConfig
 	uint32_t max_slices = 0;            // max over jobs of n_rows / 64
 	uint32_t max_rows = 0;
 	uint32_t emit_runs = 0;             // 1: no result of the batch needs a cell list: the lanes = reads kernel hands back node runs instead of moves
+	uint32_t emit_ops = 0;              // 1: GA_F_OPS: after the last pass the back end codes every job's operations as runs (ga_ops.h)
 };
 
 struct GaRunStats
@@ -76,7 +77,13 @@ struct GaEqSource
 	const GaEqFill* fills = nullptr; size_t nFills = 0;
 	const uint8_t* rowCode = nullptr; const uint8_t* rowCodeRc = nullptr;       // 256 entries each
 	uint8_t padCode = 0;
+	const uint32_t* twin = nullptr;     // per node: the node whose digraph id is this one's ^ 1 (0xffffffff: none); what GA_F_OPS mirrors backward cells with
 };
+
+// What a batch run with GaRunConfig::emit_ops hands back (ga_ops.h): job j's runs are runs[offsets[j] .. offsets[j + 1]), in the final order
+// of the job's part of the read's TraceItem list, each run type | length << 3; the HIP-event times of the counting and the writing launch;
+// the jobs coded and the moves read.  The arrays stay the back end's (valid from fetch until fetchDone or the next fetch)
+struct GaOpsOut { const uint32_t* runs = nullptr; const uint64_t* offsets = nullptr; uint64_t n_runs = 0; double count_ms = 0, write_ms = 0; uint64_t jobs = 0, moves = 0; };
 
 // ---- seeding (ga_seed.h): a k-mer index of the uploaded graph and, per batch of reads, the seeds it gives ------------------------
 struct GaSeedIndexInfo { uint64_t kmers_seen = 0, entries = 0, distinct_keys = 0, bytes = 0; double build_ms = 0; uint32_t k = 0, sample_shift = 0, dir_bits = 0; };
@@ -164,6 +171,8 @@ public:
 	// true: ga_backend_create_batch wants a GaEqSource and builds the match words on its side (the product: a kernel over the uploaded
 	// reads); false: it wants the finished words (the host emulation of tests/emul)
 	virtual bool buildsMatchWords() const { return false; }
+	// true: this back end codes operations (GaRunConfig::emit_ops); on one that does not, a prepare with GA_F_OPS is refused
+	virtual bool codesOps() const { return false; }
 	// host memory for a batch's copy of the reads (the product: pinned blocks from a pool, so that their upload is one DMA transfer)
 	virtual std::shared_ptr<char> hostBlock(size_t bytes)
 	{
@@ -186,6 +195,8 @@ public:
 	virtual int run() = 0;                                                   // device work only; returns ga_status
 	// moves of job i: (*traceBytes)[outs[i].trace_off ..+trace_len); the bytes stay the backend's (valid until fetchDone or the next fetch)
 	virtual int fetch(std::vector<GaJobOut>& outs, const uint8_t** traceBytes, uint64_t* nBytes) = 0;
+	// after fetch, of a batch run with emit_ops: the runs, their places and the launches' times; a back end without it refuses
+	virtual int fetchOps(GaOpsOut&) { return 100; }
 	virtual void fetchDone() {}
 	virtual GaRunStats stats() const = 0;
 };

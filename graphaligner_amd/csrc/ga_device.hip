@@ -19,6 +19,7 @@
 #include "ga_lanes.h"
 #include "ga_seed_dev.h"
 #include "ga_plan.h"
+#include "ga_ops.h"
 
 namespace {
 
@@ -297,6 +298,18 @@ __global__ void __launch_bounds__(256) ga_plan_write_kernel(gap::PlanLaunch L)
 	else if (s == nSlots) gap::plan_tail(L);
 }
 
+// ---- per-base operations as runs (ga_ops.h): one wave per job at a time, the same program counting and writing ------------------
+__global__ void __launch_bounds__(64) ga_ops_count_kernel(gao::OpsLaunch L)
+{
+	__shared__ gao::OpsLds lds;
+	gao::run_wave<false>(L, lds, blockIdx.x, gridDim.x);
+}
+__global__ void __launch_bounds__(64) ga_ops_write_kernel(gao::OpsLaunch L)
+{
+	__shared__ gao::OpsLds lds;
+	gao::run_wave<true>(L, lds, blockIdx.x, gridDim.x);
+}
+
 // every job's output record starts a run as "not run" (what a job keeps when no pass ever picks it up)
 __global__ void ga_outs_init_kernel(GaJobOut* outs, uint32_t n)
 {
@@ -321,6 +334,7 @@ struct DevGraph : GaBackendGraph
 {
 	std::shared_ptr<PinnedPool> pinned = std::make_shared<PinnedPool>();
 	bool buildsMatchWords() const override { return true; }
+	bool codesOps() const override { return true; }
 	std::shared_ptr<char> hostBlock(size_t bytes) override
 	{
 		const size_t two = (size_t)2 << 20;
@@ -355,6 +369,7 @@ struct DevGraph : GaBackendGraph
 	std::mutex twinLock;
 	uint32_t* dTwin = nullptr;
 	uint8_t* dRev = nullptr;
+	uint32_t* dOpsTwin = nullptr;      // the twin table alone, for GA_F_OPS batches of ga_batch_prepare (uploaded at the first of them)
 	GaBackendBatch* beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status) override;
 
 	int device = 0;
@@ -508,6 +523,7 @@ struct DevBatch : GaBackendBatch
 		if (evA) hipEventDestroy(evA);
 		if (evB) hipEventDestroy(evB);
 		for (hipEvent_t e : evP) if (e) hipEventDestroy(e);
+		for (hipEvent_t e : evO) if (e) hipEventDestroy(e);
 		if (stream) hipStreamDestroy(stream);
 	}
 	// a block of alloc() that the batch no longer needs, handed back before the batch ends
@@ -582,6 +598,21 @@ struct DevBatch : GaBackendBatch
 			if (alloc(&dSeq, src->seqBytes + 64) || alloc(&dFills, src->nFills) || alloc(&dLut, 512) || alloc(&dFlags, src->nFills) || alloc(&dRows, rowBytes)) return GA_E_DEVICE;
 			HIP_OK(hipMemsetAsync(dRows + rowBytes - 128, 0, 128, stream));
 			builtRows = dRows;
+			resSeq = dSeq; resSeqBytes = src->seqBytes; resFills = dFills;
+			if (cfg.emit_ops && src->twin)
+			{
+				std::lock_guard<std::mutex> guard(g->twinLock);
+				if (!g->dTwin && !g->dOpsTwin)
+				{
+					void* tw = nullptr;
+					HIP_OK(hipMalloc(&tw, (size_t)g->g.n_nodes * 4));
+					g->allocs.push_back(tw);
+					HIP_OK(hipMemcpyAsync(tw, src->twin, (size_t)g->g.n_nodes * 4, hipMemcpyHostToDevice, stream));
+					HIP_OK(hipStreamSynchronize(stream));
+					g->dOpsTwin = (uint32_t*)tw;
+				}
+			}
+			memcpy(opsLut, src->rowCode, 256);
 			uint8_t lut[512];
 			memcpy(lut, src->rowCode, 256); memcpy(lut + 256, src->rowCodeRc, 256);
 			HIP_OK(hipMemcpyAsync(dSeq, src->seq, src->seqBytes, hipMemcpyHostToDevice, stream));
@@ -754,6 +785,8 @@ struct DevBatch : GaBackendBatch
 		plan.seed_ms = ms[0]; plan.plan_ms = ms[1]; plan.eq_ms = ms[2];
 		if (plan.nJobs > nJobsCap || plan.rowsTotal > req.rowsBound) return GA_E_DEVICE;
 		badFills.assign(plan.badFills, plan.badFills + plan.nJobs);
+		resSeq = dIn; resSeqBytes = req.blockBytes; resFills = (const GaEqFill*)P.fills;
+		memcpy(opsLut, req.rowCode, 256);
 		builtRows = dRows;
 		L.rows = nullptr;
 		L.jobs = (const GaJob*)P.jobs;
@@ -977,7 +1010,94 @@ struct DevBatch : GaBackendBatch
 		return rc;
 	}
 
+	// ---- GA_F_OPS (ga_ops.h): after the last pass, every finished job's moves coded as runs where they lie -------------------------
+	const uint8_t* resSeq = nullptr;   // the batch's resident copy of the reads and, per job, where its rows come from in it
+	size_t resSeqBytes = 0;
+	const GaEqFill* resFills = nullptr;
+	uint8_t opsLut[256];               // the row codes of the read characters
+	hipEvent_t evO[4] = {nullptr, nullptr, nullptr, nullptr};
+	uint64_t* dOpsOffsets = nullptr;   // device copies, until fetch has brought them down
+	uint32_t* dOpsRuns = nullptr;
+	uint64_t opsTotal = 0, opsJobs = 0, opsMoves = 0;
+	float opsCountMs = 0, opsWriteMs = 0;
+	std::vector<uint64_t> opsOffsetsHost;
+	std::unique_ptr<uint32_t[]> opsRunsHost;
+	void releaseOps()
+	{
+		if (dOpsOffsets) release(dOpsOffsets);
+		if (dOpsRuns) release(dOpsRuns);
+		dOpsOffsets = nullptr; dOpsRuns = nullptr;
+	}
+	int runOps()
+	{
+		if (!resSeq || !resFills) return GA_E_INVALID;
+		const size_t n = jobs.size();
+		uint64_t* dCounts; uint8_t *dLut, *dTmp;
+		if (alloc(&dCounts, n + 1) || alloc(&dOpsOffsets, n + 1) || alloc(&dLut, 256)) return GA_E_DEVICE;
+		size_t tmpBytes = 0;
+		HIP_OK(rocprim::exclusive_scan(nullptr, tmpBytes, dCounts, dOpsOffsets, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), stream));
+		if (alloc(&dTmp, tmpBytes + 16)) return GA_E_DEVICE;
+		for (hipEvent_t& e : evO) if (!e) HIP_OK(hipEventCreate(&e));
+		HIP_OK(hipMemcpyAsync(dLut, opsLut, 256, hipMemcpyHostToDevice, stream));
+		HIP_OK(hipMemsetAsync(dCounts, 0, (n + 1) * 8, stream));
+		if (uploadList(orderHost)) return GA_E_DEVICE;           // longest first, dealt statically: wave w takes entries w, w + waves, ...
+		gao::OpsLaunch O;
+		memset(&O, 0, sizeof(O));
+		O.graph = L.graph; O.jobs = L.jobs; O.outs = L.outs; O.fills = resFills;
+		O.traces = L.traces; O.trace_bytes = L.trace_pool_cap;
+		O.seq = resSeq; O.seq_bytes = resSeqBytes; O.row_code = dLut;
+		{
+			std::lock_guard<std::mutex> guard(g->twinLock);
+			O.twin = g->dTwin ? g->dTwin : g->dOpsTwin;
+		}
+		if (!O.twin) return GA_E_INVALID;
+		O.job_list = dList; O.n_jobs = (uint32_t)n;
+		O.counts = dCounts; O.offsets = dOpsOffsets;
+		uint32_t waves = (uint32_t)std::min<size_t>(n, (size_t)g->cus * 16);
+		if (knobs.waveSlots) waves = std::min(waves, knobs.waveSlots);
+		HIP_OK(hipEventRecord(evO[0], stream));
+		hipLaunchKernelGGL(ga_ops_count_kernel, dim3(waves), dim3(64), 0, stream, O);
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipEventRecord(evO[1], stream));
+		HIP_OK(rocprim::exclusive_scan(dTmp, tmpBytes, dCounts, dOpsOffsets, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), stream));
+		HIP_OK(hipMemcpyAsync(&opsTotal, dOpsOffsets + n, 8, hipMemcpyDeviceToHost, stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		if (alloc(&dOpsRuns, opsTotal + 1)) return GA_E_DEVICE;
+		O.runs = dOpsRuns;
+		HIP_OK(hipEventRecord(evO[2], stream));
+		hipLaunchKernelGGL(ga_ops_write_kernel, dim3(waves), dim3(64), 0, stream, O);
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipEventRecord(evO[3], stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		HIP_OK(hipEventElapsedTime(&opsCountMs, evO[0], evO[1]));
+		HIP_OK(hipEventElapsedTime(&opsWriteMs, evO[2], evO[3]));
+		release(dCounts); release(dTmp); release(dLut);
+		opsJobs = opsMoves = 0;
+		for (const GaJobOut& o : outs) if (o.status == GA_OK && o.n_valid > 0 && o.reserved3 != 1) { opsJobs++; opsMoves += o.trace_len; }
+		if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: operations: %llu jobs, %llu moves, %llu runs on %u waves, count %.2f ms, write %.2f ms\n",
+		                               (unsigned long long)opsJobs, (unsigned long long)opsMoves, (unsigned long long)opsTotal, waves, opsCountMs, opsWriteMs);
+		return 0;
+	}
+	int fetchOps(GaOpsOut& out) override
+	{
+		if (!cfg.emit_ops) return GA_E_INVALID;
+		out.runs = opsRunsHost.get(); out.offsets = opsOffsetsHost.empty() ? nullptr : opsOffsetsHost.data();
+		out.n_runs = opsTotal; out.count_ms = opsCountMs; out.write_ms = opsWriteMs; out.jobs = opsJobs; out.moves = opsMoves;
+		return 0;
+	}
+
 	int run() override
+	{
+		int rc = runLadder();
+		if (rc || !cfg.emit_ops) return rc;
+		releaseOps();
+		opsTotal = opsJobs = opsMoves = 0; opsCountMs = opsWriteMs = 0;
+		opsOffsetsHost.clear(); opsRunsHost.reset();
+		if (jobs.empty()) { opsOffsetsHost.assign(1, 0); opsRunsHost.reset(new uint32_t[1]); return 0; }
+		return runOps();
+	}
+
+	int runLadder()
 	{
 		HIP_OK(hipSetDevice(g->device));
 		st = GaRunStats();
@@ -1094,6 +1214,16 @@ struct DevBatch : GaBackendBatch
 		}
 		*traces = hostTraces;
 		*nBytes = top;
+		if (cfg.emit_ops && dOpsOffsets)
+		{
+			// the runs and their places come down with the records; their buffers go back to the graph's block list
+			opsOffsetsHost.resize(jobs.size() + 1);
+			opsRunsHost.reset(new uint32_t[opsTotal + 1]);
+			HIP_OK(hipMemcpyAsync(opsOffsetsHost.data(), dOpsOffsets, opsOffsetsHost.size() * 8, hipMemcpyDeviceToHost, stream));
+			if (opsTotal) HIP_OK(hipMemcpyAsync(opsRunsHost.get(), dOpsRuns, opsTotal * 4, hipMemcpyDeviceToHost, stream));
+			HIP_OK(hipStreamSynchronize(stream));
+			releaseOps();
+		}
 		return 0;
 	}
 	void fetchDone() override

@@ -342,6 +342,8 @@ struct ga_batch
 	GaSeedParams seedParams{};
 	std::vector<uint32_t> seedOutN, seedOut, seedOutLocus, seedNLoci;
 	double seedMs = 0, planMs = 0, eqMs = 0, hostMs = 0;
+	// GA_F_OPS: where the runs of the last collect's aligned reads came from
+	uint64_t opsFromDevice = 0, opsFromHost = 0;
 	~ga_batch() { delete dev; }
 };
 
@@ -438,8 +440,10 @@ struct ResultsOwner
 	std::vector<ga_mapping_t> mappings;
 	std::vector<char> edits;
 	std::vector<ga_trace_item_t> trace;
+	std::vector<ga_read_ops_t> readOps;
+	std::vector<uint32_t> ops;
 	// the arrays of a whole batch (hundreds of MB, not cleared first): from the process-wide pool below, back to it with the results
-	PooledBuffer allReads, allMappings, allTrace;
+	PooledBuffer allReads, allMappings, allTrace, allReadOps, allOps;
 	std::shared_ptr<char> seqKeep;        // edit_bytes of a batch's results = the batch's copy of the reads, kept alive here
 };
 
@@ -793,10 +797,11 @@ static void decideRuns(ga_batch* b)
 		const double meanNode = g->nodeCount() > 2 ? (double)g->bases.size() / (double)(g->nodeCount() - 2) : 64.0;
 		// (with the words built by the back end, whether a row is such a character is known when the batch has been created: the back
 		// end clears the flag then)
-		bool runs = (b->flags & GA_F_TRACE) == 0 && b->anyInvalidRow.load() == 0 && meanNode >= 40 && !(getenv("GA_RUNS") && atoi(getenv("GA_RUNS")) == 0);
+		bool runs = (b->flags & (GA_F_TRACE | GA_F_OPS)) == 0 && b->anyInvalidRow.load() == 0 && meanNode >= 40 && !(getenv("GA_RUNS") && atoi(getenv("GA_RUNS")) == 0);
 		for (size_t i = 0; i < b->reads.size() && runs; i++) if (b->reads[i].nSeeds > 1) runs = false;
 		for (const SeedPlan& sp : b->seeds) if (sp.bwJob >= 0 || (sp.fwJob >= 0 && sp.pos != 0)) { runs = false; break; }
 		b->cfg.emit_runs = runs ? 1u : 0u;
+		b->cfg.emit_ops = (b->flags & GA_F_OPS) ? 1u : 0u;
 	}
 }
 
@@ -806,6 +811,7 @@ int ga_batch_prepare(const ga_graph_t* g, const ga_read_t* reads, size_t nReads,
 	if (!g || !out || (!reads && nReads) || !seedOffsets) return GA_E_INVALID;
 	if (!g->finalized) return GA_E_NOT_FINALIZED;
 	if (!g->device) return GA_E_NO_DEVICE;
+	if ((flags & GA_F_OPS) && !g->device->codesOps()) return GA_E_INVALID;
 	const CharTables& T = tables();
 	ga_batch* b = new ga_batch();
 	b->g = g;
@@ -947,6 +953,7 @@ int ga_batch_prepare(const ga_graph_t* g, const ga_read_t* reads, size_t nReads,
 	src.seq = b->seqBuf; src.seqBytes = b->seqBufBytes;
 	src.fills = eqFills.data(); src.nFills = eqFills.size();
 	src.rowCode = T.rowCode; src.rowCodeRc = T.rowCodeRc; src.padCode = T.rowCode[(uint8_t)'N'];
+	src.twin = g->twin.data();
 	b->dev = ga_backend_create_batch(g->device, [b]() -> const std::vector<uint8_t>& { buildRows(b); return b->rows; }, b->eq.get(), deviceWords ? &src : nullptr, b->eqWords,
 	                                 b->jobs, b->cfg, &status);
 	if (!b->dev) { delete b; return status ? status : GA_E_DEVICE; }
@@ -976,6 +983,7 @@ int ga_batch_prepare_seeded(const ga_graph_t* g, const ga_read_t* reads, size_t 
 	if (!g->device) return GA_E_NO_DEVICE;
 	GaSeedEngine* eng = g->device->seedEngine();
 	if (!eng || !eng->built()) return GA_E_INVALID;
+	if ((flags & GA_F_OPS) && !g->device->codesOps()) return GA_E_INVALID;
 	GaSeedParams p{15, 2, 8, 4096, 1024, 64, 2, 2};                             // (ga_seed_params_default)
 	if (params) p = GaSeedParams{params->k, params->sample_shift, params->max_occ, params->max_hits, params->window, params->diag_tol, params->min_support, params->max_seeds};
 	if (!(p.k >= 11 && p.k <= 31 && p.sample_shift <= 8 && p.max_hits >= 1 && p.max_hits <= 65536 && p.max_seeds >= 1 && p.max_seeds <= 64)) return GA_E_INVALID;
@@ -1209,6 +1217,20 @@ int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out)
 	return GA_S_OK;
 }
 
+int ga_batch_ops_stats(const ga_batch_t* b, ga_batch_ops_stats_t* out)
+{
+	if (!b || !out || !b->dev || !(b->flags & GA_F_OPS)) return GA_E_INVALID;
+	memset(out, 0, sizeof(*out));
+	GaOpsOut o;
+	if (b->ran && b->dev->fetchOps(o) == 0)
+	{
+		out->count_kernel_ms = o.count_ms; out->write_kernel_ms = o.write_ms;
+		out->jobs_coded = o.jobs; out->moves_read = o.moves; out->runs_written = o.n_runs;
+	}
+	out->reads_from_device = b->opsFromDevice; out->reads_from_host = b->opsFromHost;
+	return GA_S_OK;
+}
+
 int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 {
 	if (!b || !out || !b->dev || !b->ran) return GA_E_INVALID;
@@ -1219,6 +1241,11 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 	const auto t0 = std::chrono::steady_clock::now();
 	int s = b->dev->fetch(outs, &moves, &nMoveBytes);
 	if (s) return s;
+	// GA_F_OPS: every job's runs as the back end coded them (ga_ops.h), in the final order of the job's part of the TraceItem list
+	const bool wantOps = (b->flags & GA_F_OPS) != 0;
+	GaOpsOut devOps;
+	if (wantOps && (s = b->dev->fetchOps(devOps)) != 0) { b->dev->fetchDone(); return s; }
+	if (wantOps && !outs.empty() && (!devOps.runs || !devOps.offsets)) { b->dev->fetchDone(); return GA_E_DEVICE; }
 	const auto t1 = std::chrono::steady_clock::now();
 	b->columnUpdates = 0;
 	b->slicesRun = 0;
@@ -1264,18 +1291,62 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 	// edit_seq_off and first_trace / n_trace say where each read's entries are.
 	const size_t nReadsAll = b->reads.size();
 	const bool wantTraceAll = (b->flags & GA_F_TRACE) != 0;
-	std::vector<uint64_t> mapAt(nReadsAll + 1, 0), editAt(nReadsAll + 1, 0), traceAt(nReadsAll + 1, 0);
+	std::vector<uint64_t> mapAt(nReadsAll + 1, 0), editAt(nReadsAll + 1, 0), traceAt(nReadsAll + 1, 0), opsAt(wantOps ? nReadsAll + 1 : 0, 0);
+	// GA_F_OPS: reads whose runs are derived here from the TraceItem list instead (include/graphaligner_amd.h: GA_F_OPS): a character
+	// outside IUPAC (the item pass decides the read's status), and a forward part that the reference leaves unshifted (:3091-3094)
+	// or whose rows it does not cut at the overlap (the unsigned difference of :3051 wraps) -- there the device's characters are not
+	// the list's
+	std::vector<uint8_t> opsOnHost(wantOps ? nReadsAll : 0, 0);
 	for (size_t ri = 0; ri < nReadsAll; ri++)
 	{
 		const ReadPlan& rp = b->reads[ri];
-		uint64_t runs = 1, items = 0;
+		uint64_t runs = 1, items = 0, opRuns = 0;
 		for (size_t k = rp.firstSeed; k < rp.firstSeed + rp.nSeeds; k++)
+		{
 			for (int64_t job : {b->seeds[k].bwJob, b->seeds[k].fwJob})
-				if (job >= 0 && outs[job].status == GA_OK) { runs += (uint64_t)outs[job].n_node_steps + 1; items += (uint64_t)outs[job].trace_len + 2; }
+				if (job >= 0 && outs[job].status == GA_OK)
+				{
+					runs += (uint64_t)outs[job].n_node_steps + 1; items += (uint64_t)outs[job].trace_len + 2;
+					if (wantOps) opRuns += devOps.offsets[job + 1] - devOps.offsets[job] + 1;
+				}
+			if (wantOps)
+			{
+				const SeedPlan& sp = b->seeds[k];
+				if (sp.fwJob >= 0 && sp.pos > 0 && !(sp.bwJob >= 0 && outs[sp.bwJob].n_valid > 0)) opsOnHost[ri] = 1;
+				if (sp.fwJob >= 0 && b->seqs[ri].size() - sp.pos < (uint64_t)g.dbgOverlap) opsOnHost[ri] = 1;
+			}
+		}
 		mapAt[ri + 1] = mapAt[ri] + runs;
 		editAt[ri + 1] = editAt[ri] + b->seqs[ri].size();
 		traceAt[ri + 1] = traceAt[ri] + (wantTraceAll ? items : 0);
+		if (wantOps)
+		{
+			if (b->readInvalid[ri].load(std::memory_order_relaxed)) opsOnHost[ri] = 1;
+			opsAt[ri + 1] = opsAt[ri] + (opsOnHost[ri] ? items : opRuns);
+		}
 	}
+	ga_read_ops_t* const allReadOps = wantOps ? (ga_read_ops_t*)R->allReadOps.get((nReadsAll + 1) * sizeof(ga_read_ops_t)) : nullptr;
+	uint32_t* const allOps = wantOps ? (uint32_t*)R->allOps.get((opsAt[nReadsAll] + 1) * sizeof(uint32_t)) : nullptr;
+	if (wantOps && (!allReadOps || !allOps)) { delete R; b->dev->fetchDone(); return GA_E_INVALID; }
+	std::atomic<uint64_t> opsFromDevice{0}, opsFromHost{0};
+	// a read's finished runs into its place, with the four counts
+	auto storeOps = [&](size_t ri, const std::vector<uint32_t>& runsOfRead, bool fromHost) -> bool {
+		if (runsOfRead.size() > opsAt[ri + 1] - opsAt[ri]) return false;
+		ga_read_ops_t& ro = allReadOps[ri];
+		ro.n_ops = (uint32_t)runsOfRead.size();
+		uint32_t sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+		for (size_t k = 0; k < runsOfRead.size(); k++) { allOps[opsAt[ri] + k] = runsOfRead[k]; sum[runsOfRead[k] & 7u] += runsOfRead[k] >> 3; }
+		ro.n_match = sum[GA_OP_MATCH]; ro.n_mismatch = sum[GA_OP_MISMATCH]; ro.n_insertion = sum[GA_OP_INSERTION]; ro.n_deletion = sum[GA_OP_DELETION];
+		if (!fromHost) opsFromDevice++;                         // (a read on the host path was counted when its item pass ran)
+		return true;
+	};
+	// the winning seed's runs: backward job, one SPLIT run when both parts have cells, forward job
+	auto deviceOps = [&](int64_t bwJob, bool bwCells, int64_t fwJob, bool fwCells, std::vector<uint32_t>& into) {
+		into.clear();
+		if (bwCells && bwJob >= 0) into.insert(into.end(), devOps.runs + devOps.offsets[bwJob], devOps.runs + devOps.offsets[bwJob + 1]);
+		if (bwCells && fwCells) into.push_back(GA_OP_SPLIT | (1u << 3));
+		if (fwCells && fwJob >= 0) into.insert(into.end(), devOps.runs + devOps.offsets[fwJob], devOps.runs + devOps.offsets[fwJob + 1]);
+	};
 	ga_read_result_t* const allReads = (ga_read_result_t*)R->allReads.get((nReadsAll + 1) * sizeof(ga_read_result_t));
 	ga_mapping_t* const allMappings = (ga_mapping_t*)R->allMappings.get((mapAt[nReadsAll] + 1) * sizeof(ga_mapping_t));
 	// (no copy of the edit sequences: they are pieces of the reads, and the results share the batch's read buffer)
@@ -1292,7 +1363,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 	struct NodeRun { uint32_t node, firstOffset, lastOffset; uint64_t firstRow, lastRow; };
 	auto forwardOnly = [&](size_t ri, ga_read_result_t& rr) -> bool {
 		const ReadPlan& rp = b->reads[ri];
-		if (rp.nSeeds != 1 || wantTraceAll) return false;
+		if (rp.nSeeds != 1 || wantTraceAll || (wantOps && opsOnHost[ri])) return false;
 		const SeedPlan& sp = b->seeds[rp.firstSeed];
 		if (sp.early != GA_S_OK || sp.bwJob >= 0 || sp.fwJob < 0 || sp.pos != 0) return false;
 		const GaJobOut& o = outs[sp.fwJob];
@@ -1391,6 +1462,12 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 			allMappings[mapAt[ri] + k] = m;
 			beforeRow = r.lastRow;
 		}
+		if (wantOps)
+		{
+			thread_local std::vector<uint32_t> opRuns;
+			deviceOps(-1, false, sp.fwJob, true, opRuns);
+			if (!storeOps(ri, opRuns, false)) { overflow.store(1); rr.status = GA_E_DEVICE; return true; }
+		}
 		rr.failed = 0;
 		rr.score = o.score;
 		rr.n_mappings = nRuns;
@@ -1403,6 +1480,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 
 	auto work = [&](size_t lo, size_t hi) {
 	std::vector<ga_trace_item_t> items;
+	std::vector<uint32_t> opRuns;
 	uint64_t columnUpdates = 0;
 	for (size_t ri = lo; ri < hi; ri++)
 	{
@@ -1412,6 +1490,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 		rr.score = kMax;
 		rr.first_mapping = mapAt[ri];
 		rr.first_trace = traceAt[ri];
+		if (wantOps) { memset(&allReadOps[ri], 0, sizeof(ga_read_ops_t)); allReadOps[ri].first_op = opsAt[ri]; }
 		const ReadSeq& seq = b->seqs[ri];
 		const ReadPlan& rp = b->reads[ri];
 		if (rp.nSeeds == 0) { rr.status = GA_S_ASSERTION; continue; }          // assert(seedHits.size() > 0) (:412)
@@ -1421,6 +1500,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 		uint64_t bestEstimate = 0, bestPos = 0;
 		Trace bestFw, bestBw;
 		int32_t bestFwScore = 0, bestBwScore = 0;
+		int64_t bestFwJob = -1, bestBwJob = -1;
 		int status = GA_S_OK;
 		for (size_t k = rp.firstSeed; k < rp.firstSeed + rp.nSeeds && status == GA_S_OK; k++)
 		{
@@ -1478,6 +1558,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 			{
 				bestFw = std::move(fw); bestBw = std::move(bw); bestFwScore = fwScore; bestBwScore = bwScore;
 				bestEstimate = estimate; bestPos = sp.pos; have = true;
+				bestFwJob = sp.fwJob; bestBwJob = sp.bwJob;
 			}
 		}
 		rr.status = status;
@@ -1487,11 +1568,25 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 		// non-IUPAC read character; only reads that contain one need the scan when no trace is wanted
 		bool wantTrace = wantTraceAll;
 		bool suspicious = false;
-		if (!wantTrace) for (char c : seq) if (tables().rowCode[(uint8_t)c] & GA_ROW_INVALID) { suspicious = true; break; }
+		if (!wantTrace || wantOps) for (char c : seq) if (tables().rowCode[(uint8_t)c] & GA_ROW_INVALID) { suspicious = true; break; }
 		items.clear();
-		if (wantTrace || suspicious)
+		// (a character outside IUPAC that no job's rows show as such -- 'U' in a backward part, which ReverseComplement maps -- is found
+		// by this scan; the device's runs of such a read are within the bound its place was sized with, and storeOps checks it)
+		const bool hostOps = wantOps && (opsOnHost[ri] || suspicious);
+		if (wantTrace || suspicious || hostOps)
 		{
 			bool fine = traceItems(g, seq, bestBw, bestFw, items);
+			if (hostOps) opsFromHost++;
+			if (hostOps && fine)
+			{
+				// the list's types cut into maximal runs
+				opRuns.clear();
+				for (const ga_trace_item_t& it : items)
+				{
+					if (!opRuns.empty() && (opRuns.back() & 7u) == (uint32_t)it.type) opRuns.back() += 1u << 3;
+					else opRuns.push_back((uint32_t)it.type | (1u << 3));
+				}
+			}
 			if (!wantTrace || !fine) items.clear();
 			if (!fine) { rr.status = GA_S_ASSERTION; continue; }
 		}
@@ -1506,6 +1601,11 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 			overflow.store(1);              // (a bound above is wrong: fail loudly instead of writing past a read's place)
 			rr.status = GA_E_DEVICE;
 			continue;
+		}
+		if (wantOps)
+		{
+			if (!hostOps) deviceOps(bestBwJob, !bestBw.empty(), bestFwJob, !bestFw.empty(), opRuns);
+			if (!storeOps(ri, opRuns, hostOps)) { overflow.store(1); rr.status = GA_E_DEVICE; continue; }
 		}
 		rr.failed = 0;
 		rr.score = merged.score;
@@ -1548,6 +1648,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 		for (auto& th : pool) th.join();
 	}
 	b->columnUpdates += columnUpdatesAll.load();
+	b->opsFromDevice = opsFromDevice.load(); b->opsFromHost = opsFromHost.load();
 	b->dev->fetchDone();
 	const auto t2 = std::chrono::steady_clock::now();
 	if (overflow.load()) { delete R; return GA_E_DEVICE; }
@@ -1555,6 +1656,7 @@ int ga_batch_collect(ga_batch_t* b, ga_results_t** out)
 	R->pub.n_mappings = mapAt[nReadsAll]; R->pub.mappings = allMappings;
 	R->pub.n_edit_bytes = b->seqBufBytes; R->pub.edit_bytes = allEdits;
 	R->pub.n_trace = traceAt[nReadsAll]; R->pub.trace = allTrace;
+	R->pub.read_ops = allReadOps; R->pub.n_ops = wantOps ? opsAt[nReadsAll] : 0; R->pub.ops = allOps;
 	*out = &R->pub;
 	if (getenv("GA_DEBUG_COLLECT"))
 	{
@@ -1637,11 +1739,21 @@ int ga_results_unsplit(const ga_graph_t* g, const ga_results_t* in, ga_results_t
 		rr.first_mapping = firstMap; rr.n_mappings = R->mappings.size() - firstMap;
 		rr.first_trace = firstTrace; rr.n_trace = R->trace.size() - firstTrace;
 		R->reads.push_back(rr);
+		if (in->read_ops)
+		{
+			// (runs pass through unchanged: types do not depend on where nodes are cut)
+			ga_read_ops_t ro = in->read_ops[i];
+			const uint64_t from = ro.first_op;
+			ro.first_op = R->ops.size();
+			R->ops.insert(R->ops.end(), in->ops + from, in->ops + from + ro.n_ops);
+			R->readOps.push_back(ro);
+		}
 	}
 	R->pub.n_reads = R->reads.size(); R->pub.reads = R->reads.data();
 	R->pub.n_mappings = R->mappings.size(); R->pub.mappings = R->mappings.data();
 	R->pub.n_edit_bytes = R->edits.size(); R->pub.edit_bytes = R->edits.data();
 	R->pub.n_trace = R->trace.size(); R->pub.trace = R->trace.data();
+	if (in->read_ops) { R->pub.read_ops = R->readOps.data(); R->pub.n_ops = R->ops.size(); R->pub.ops = R->ops.data(); }
 	*out = &R->pub;
 	return GA_S_OK;
 }

@@ -1,0 +1,302 @@
+// ga_ops.h -- per-base alignment operations, run-length coded on the device (include/graphaligner_amd.h states the rule under GA_F_OPS;
+// DESIGN.md section 11 argues it).  After the last pass of the ladder every finished job's traceback lies in the trace pool as one byte
+// per move (ga_types.h: GA_MOVE_*).  This program walks those bytes where they lie and leaves, per job, the types of the TraceItems
+// the job contributes (getTraceInfoInner, GraphAligner.h:718-780; traceItemsInner of ga_host.cpp) cut into maximal runs of equal type.
+//
+// One wave (= one workgroup of 64 lanes) takes one job at a time and walks its moves 64 per round.  Written in PHASES like ga_seed.h:
+// inside GAO_LANES(l) { ... } every lane runs the block for its own l; lanes exchange values only through the OpsLds block with a
+// sync() between the phase that writes and the phase that reads, and through the two wave primitives below (scan, ballot).  Everything
+// declared outside a lane block is the same in every lane, so the control flow around the blocks is uniform.  On gfx950 a lane block
+// is straight-line code of the lane; in the host build of the tests (tests/emul_ops) it is a loop over the 64 lanes.
+//
+// The same program runs twice: a counting launch leaves one run count per job, an exclusive scan turns the counts into places, and a
+// writing launch stores the runs there -- a backward job's in stream order, a forward job's back to front, which is the final order
+// of both (reverseTrace, GraphAligner.h:3026-3037).  Jobs are dealt statically (wave w takes entries w, w + waves, ... of the job
+// list) and every loop ends by a known count.
+#pragma once
+#include "ga_backend.h"
+
+namespace gao {
+
+#ifdef GA_EMULATE
+#define GAO_FN inline
+#define GAO_LANES(l) for (int l = 0; l < 64; l++)
+inline void sync() {}
+#else
+#define GAO_FN __device__ __forceinline__
+#define GAO_LANES(l) if (const int l = (int)threadIdx.x; true)
+GAO_FN void sync() { __syncthreads(); }
+#endif
+
+enum { OP_MATCH = 1, OP_MISMATCH = 2, OP_INSERTION = 3, OP_DELETION = 4, OP_SPLIT = 5 };
+
+struct OpsLaunch
+{
+	GaDevGraph graph;
+	const GaJob* jobs;
+	const GaJobOut* outs;
+	const GaEqFill* fills;                 // per job: where its rows come from in `seq`
+	const uint8_t* traces;                 // the trace pool
+	uint64_t trace_bytes;                  // its size: a job whose moves would leave it is not walked
+	const uint8_t* seq;                    // the batch's resident copy of the reads
+	uint64_t seq_bytes;
+	const uint8_t* row_code;               // 256 entries: bits 0-3 = which of A, C, G, T the character matches
+	const uint32_t* twin;                  // [n_nodes] the node of the other strand (0xffffffff: none); nullptr: the strands are exact mirrors
+	const uint32_t* job_list;              // optional hand-out order; nullptr = identity
+	uint32_t n_jobs, reserved;
+	uint64_t* counts;                      // [n_jobs + 1] counting launch: runs per job (entry n_jobs stays 0)
+	const uint64_t* offsets;               // [n_jobs + 1] writing launch: the scanned counts
+	uint32_t* runs;                        // writing launch: type | length << 3
+};
+
+struct OpsLds
+{
+	uint8_t code[256];
+	uint32_t own[64];                      // the lane's move: row step | column step << 16
+	uint32_t incl[64];                     // inclusive sums of own
+	uint32_t colLane[64];                  // colLane[c] = the lane whose move is the round's c-th column step
+	// per cell of the round (cell l = where move l starts; cell 64 = where the round ends): its node, the column steps of the round
+	// after which that node's offset 0 is reached, the node's length and first column
+	uint32_t cNode[65], cTop[65], cLen[65];
+	uint64_t cCol0[65];
+	uint8_t mv[64], type[64], flag[64];
+};
+
+// inclusive scan of lds.own over the lanes into lds.incl (the caller syncs before and after)
+GAO_FN void scan_steps(OpsLds& lds)
+{
+#ifdef GA_EMULATE
+	uint32_t run = 0;
+	for (int l = 0; l < 64; l++) { run += lds.own[l]; lds.incl[l] = run; }
+#else
+	const int l = (int)threadIdx.x;
+	uint32_t v = lds.own[l];
+	for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64); if (l >= d) v += o; }
+	lds.incl[l] = v;
+#endif
+}
+
+// bit l = lane l's byte is not zero (the caller syncs before)
+GAO_FN uint64_t ballot(const uint8_t* flag)
+{
+#ifdef GA_EMULATE
+	uint64_t m = 0;
+	for (int l = 0; l < 64; l++) if (flag[l]) m |= 1ull << l;
+	return m;
+#else
+	return __ballot(flag[threadIdx.x] != 0);
+#endif
+}
+
+GAO_FN uint32_t popc(uint64_t x) { return (uint32_t)__builtin_popcountll(x); }
+GAO_FN uint32_t ctz(uint64_t x) { return (uint32_t)__builtin_ctzll(x); }
+
+// a node of length 1 that has itself as out-neighbour: a step up in its column is a diagonal to the reference (GraphAligner.h:742)
+GAO_FN bool self_loop(const GaDevGraph& g, uint32_t node)
+{
+	const uint32_t lo = g.out_off[node], hi = g.out_off[node + 1];
+	bool found = false;
+	for (uint32_t e = lo; e < hi; e++) found = found || g.out_nbr[e] == node;
+	return found;
+}
+
+// the runs of one job: returns their number; WRITE stores them at the job's scanned place
+template <bool WRITE> GAO_FN uint32_t walk_job(const OpsLaunch& L, OpsLds& lds, uint32_t job)
+{
+	const GaDevGraph& G = L.graph;
+	const GaJobOut* o = L.outs + job;
+	const uint32_t nMoves = o->trace_len;
+	if (o->status != GA_OK || o->n_valid == 0 || o->reserved3 == 1 || nMoves == 0) return 0;
+	const uint64_t traceOff = o->trace_off;
+	if (traceOff + nMoves > L.trace_bytes || o->start_node >= G.n_nodes) return 0;
+	const uint8_t* mv = L.traces + traceOff;
+	const uint32_t traceRows = L.jobs[job].trace_rows;
+	const GaEqFill f = L.fills[job];
+	const bool backward = f.backward != 0;
+	const uint64_t totalBp = G.node_start[G.n_nodes];
+	// the walk's state at the round's first move: the node, the column steps after which its offset 0 is reached (= the offset), the row
+	uint32_t node = o->start_node, top = o->start_offset, row0 = o->start_row;
+	const uint32_t* rec = G.node_rec + (uint64_t)node * GA_NODE_REC_WORDS;
+	uint32_t len = rec[2];
+	uint64_t col0 = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+	if (top >= len) return 0;
+	uint64_t base = 0, cnt = 0;
+	if (WRITE) { base = L.offsets[job]; cnt = L.offsets[job + 1] - base; }
+	uint32_t opened = 0, carryType = 0, carryLen = 0;       // runs opened so far; the open run
+	bool bad = false;
+	for (uint32_t m0 = 0; m0 < nMoves && !bad; m0 += 64)
+	{
+		const uint32_t nValid = nMoves - m0 < 64 ? nMoves - m0 : 64;
+		sync();                                                // (the round before is no longer read)
+		GAO_LANES(l)
+		{
+			uint32_t s = 0;
+			uint8_t b = 0;
+			if ((uint32_t)l < nValid)
+			{
+				b = mv[m0 + (uint32_t)l];
+				const uint32_t code = b & 3u;
+				s = (code != GA_MOVE_LEFT ? 1u : 0u) | (code != GA_MOVE_UP ? 0x10000u : 0u);
+			}
+			lds.mv[l] = b;
+			lds.own[l] = s;
+		}
+		sync();
+		scan_steps(lds);
+		sync();
+		const uint32_t totalRows = lds.incl[63] & 0xffffu, totalCols = lds.incl[63] >> 16;
+		GAO_LANES(l)
+		{
+			const uint32_t cb = (lds.incl[l] - lds.own[l]) >> 16;
+			if (lds.own[l] >> 16) lds.colLane[cb] = (uint32_t)l;
+			lds.cNode[l] = node; lds.cTop[l] = top; lds.cLen[l] = len; lds.cCol0[l] = col0;
+		}
+		sync();
+		// node crossings inside the round: the column step number `top` leaves offset 0 through the in-neighbour its move names; the
+		// cells behind it re-base on that neighbour.  Each crossing consumes a column step: at most 64 per round
+		for (uint32_t k = 0; k < 64 && top < totalCols; k++)
+		{
+			const uint32_t via = (uint32_t)lds.mv[lds.colLane[top]] >> 2;
+			const uint32_t inLo = G.in_off[node], inHi = G.in_off[node + 1];
+			if (via >= inHi - inLo) { bad = true; break; }
+			const uint32_t next = via < 4 ? rec[8 + via] : G.in_nbr[inLo + via];
+			if (next >= G.n_nodes) { bad = true; break; }
+			node = next;
+			rec = G.node_rec + (uint64_t)node * GA_NODE_REC_WORDS;
+			len = rec[2];
+			col0 = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+			const uint32_t from = top + 1;
+			top += len;
+			GAO_LANES(l)
+			{
+				const uint32_t cb = (lds.incl[l] - lds.own[l]) >> 16;
+				if (cb >= from) { lds.cNode[l] = node; lds.cTop[l] = top; lds.cLen[l] = len; lds.cCol0[l] = col0; }
+			}
+		}
+		if (bad || top < totalCols) { bad = true; break; }     // (a node of length 0, or a move that names no in-neighbour: nothing the kernels write)
+		GAO_LANES(l) { if (l == 0) { lds.cNode[64] = node; lds.cTop[64] = top; lds.cLen[64] = len; lds.cCol0[64] = col0; } }
+		sync();
+		GAO_LANES(l)
+		{
+			uint32_t t = 0;
+			const uint32_t excl = lds.incl[l] - lds.own[l];
+			const uint32_t rowA = row0 - (excl & 0xffffu);
+			if ((uint32_t)l < nValid && rowA < traceRows)        // cells at rows >= trace_rows are dropped: the first moves of the stream
+			{
+				const uint32_t code = lds.mv[l] & 3u;
+				if (code == GA_MOVE_LEFT) t = OP_DELETION;
+				else
+				{
+					// forward: the item describes the cell the move starts in; backward: the cell it leads to
+					const int ci = backward ? l + 1 : l;
+					const uint32_t cb = backward ? lds.incl[l] >> 16 : excl >> 16;
+					uint32_t cn = lds.cNode[ci], cl = lds.cLen[ci];
+					uint64_t col = lds.cCol0[ci] + (lds.cTop[ci] - cb);
+					bool flip = false;
+					if (backward)
+					{
+						// the final trace holds the mirror cell (reverseTrace): the other strand's node, the offset counted from its end.  On a
+						// graph with overlaps that node is not the exact reverse complement, so its own base is read
+						if (!L.twin) flip = true;
+						else
+						{
+							const uint32_t other = L.twin[cn];
+							if (other >= G.n_nodes) cn = 0;                // (no mirror: the read ends in the assertion and has no runs)
+							else
+							{
+								const uint32_t* orec = G.node_rec + (uint64_t)other * GA_NODE_REC_WORDS;
+								const uint32_t off = lds.cTop[ci] - cb;
+								col = ((uint64_t)orec[0] | ((uint64_t)orec[1] << 32)) + (orec[2] - 1 - off);
+								cl = orec[2];
+								cn = off < orec[2] ? other : 0;
+							}
+						}
+					}
+					bool diagonal = code == GA_MOVE_DIAG;
+					if (!diagonal) { if (cl == 1 && self_loop(G, cn)) diagonal = true; else t = OP_INSERTION; }
+					if (diagonal)
+					{
+						const uint32_t row = backward ? rowA - 1 : rowA;
+						const uint64_t at = f.seq_off + (backward ? (uint64_t)traceRows - 1 - row : (uint64_t)f.pos + row);
+						bool match = false;
+						if (cn != 0 && cn != G.n_nodes - 1 && at < L.seq_bytes && col < totalBp)      // (a cell on a dummy node matches nothing)
+						{
+							uint32_t b = (G.seq2[col >> 4] >> ((col & 15) * 2)) & 3u;
+							if (flip) b = 3u - b;
+							match = ((lds.code[L.seq[at]] >> b) & 1u) != 0;
+						}
+						t = match ? OP_MATCH : OP_MISMATCH;
+					}
+				}
+			}
+			lds.type[l] = (uint8_t)t;
+		}
+		sync();
+		GAO_LANES(l)
+		{
+			const uint32_t t = lds.type[l], prev = l == 0 ? carryType : lds.type[l - 1];
+			lds.flag[l] = t != 0 && t != prev ? 1 : 0;
+		}
+		sync();
+		const uint64_t starts = ballot(lds.flag), active = ballot(lds.type);
+		const uint32_t nActive = popc(active);
+		if (!starts) carryLen += nActive;
+		else
+		{
+			// every start but the round's last opens a run that also ends in this round; the first one ends the run carried in
+			const uint32_t first = ctz(starts), last = 63u - (uint32_t)__builtin_clzll(starts), firstActive = ctz(active);
+			if (WRITE)
+			{
+				GAO_LANES(l)
+				{
+					if (l == 0 && carryType)
+					{
+						const uint64_t idx = opened - 1;
+						if (idx < cnt) L.runs[base + (backward ? idx : cnt - 1 - idx)] = carryType | ((carryLen + first - firstActive) << 3);
+					}
+					if (((starts >> l) & 1) && (uint32_t)l != last)
+					{
+						const uint64_t rest = starts & ~((2ull << l) - 1);
+						const uint64_t idx = opened + popc(starts & ((1ull << l) - 1));
+						if (idx < cnt) L.runs[base + (backward ? idx : cnt - 1 - idx)] = lds.type[l] | ((ctz(rest) - (uint32_t)l) << 3);
+					}
+				}
+			}
+			carryType = lds.type[last];
+			carryLen = firstActive + nActive - last;
+			opened += popc(starts);
+		}
+		top -= totalCols;
+		row0 -= totalRows;
+	}
+	if (bad) return 0;
+	if (WRITE && carryType)
+	{
+		GAO_LANES(l)
+		{
+			const uint64_t idx = opened - 1;
+			if (l == 0 && idx < cnt) L.runs[base + (backward ? idx : cnt - 1 - idx)] = carryType | (carryLen << 3);
+		}
+	}
+	return opened;
+}
+
+// one wave's share of a launch: entries wave, wave + nWaves, ... of the job list
+template <bool WRITE> GAO_FN void run_wave(const OpsLaunch& L, OpsLds& lds, uint32_t wave, uint32_t nWaves)
+{
+	GAO_LANES(l) { for (uint32_t i = (uint32_t)l; i < 256; i += 64) lds.code[i] = L.row_code[i]; }
+	sync();
+	const uint32_t per = nWaves ? (L.n_jobs + nWaves - 1) / nWaves : 0;
+	for (uint32_t k = 0; k < per; k++)
+	{
+		const uint32_t at = wave + k * nWaves;
+		if (at >= L.n_jobs) break;
+		const uint32_t job = L.job_list ? L.job_list[at] : at;
+		if (job >= L.n_jobs) continue;
+		const uint32_t n = walk_job<WRITE>(L, lds, job);
+		if (!WRITE) { GAO_LANES(l) { if (l == 0) L.counts[job] = n; } }
+		sync();
+	}
+}
+
+}  // namespace gao

@@ -167,6 +167,18 @@ def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chu
         raise RuntimeError("work queue %s: chunks %s came back for %d chunks" % (counter.key, got[:20], len(chunks)))
     if gam:
         return b"".join(res for _, res in sorted(mine, key=lambda kr: kr[0]))
+    if summary and mine and isinstance(mine[0][1], tuple):
+        # flags with GA_F_OPS: per chunk (records, op counts, runs per read), merged the same way
+        out = np.zeros(len(reads), dtype=mine[0][1][0].dtype)
+        counts = np.zeros((len(reads), 4), dtype=np.int64)
+        runs = [None] * len(reads)
+        for k, (recs, cnt, rr) in mine:
+            idx = np.asarray(chunks[k], dtype=np.int64)
+            out[idx] = recs
+            counts[idx] = cnt
+            for i, r in zip(chunks[k], rr):
+                runs[i] = r
+        return out, counts, runs
     if summary:
         out = np.zeros(len(reads), dtype=mine[0][1].dtype) if mine else np.zeros(0)
         for k, res in mine:

@@ -143,6 +143,17 @@ typedef struct ga_read_result {
 	uint64_t column_updates;                /* band columns computed for this read (first pass) */
 } ga_read_result_t;
 
+/* per read with GA_F_OPS: its runs are results->ops[first_op .. first_op + n_ops); the four counts are summed run lengths */
+typedef struct ga_read_ops {
+	uint64_t first_op;
+	uint32_t n_ops, n_match, n_mismatch, n_insertion, n_deletion, reserved;
+} ga_read_ops_t;
+#define GA_OP_MATCH 1u
+#define GA_OP_MISMATCH 2u
+#define GA_OP_INSERTION 3u
+#define GA_OP_DELETION 4u
+#define GA_OP_SPLIT 5u
+
 /* The three arrays behind `reads` are written by several host threads at places fixed before the lengths are known, so they have GAPS:
  * n_mappings / n_edit_bytes / n_trace are the arrays' extents, not counts of valid entries, and the bytes between one read's entries
  * and the next's are unspecified (recycled memory).  Valid entries are exactly those a read's record points at:
@@ -157,11 +168,40 @@ typedef struct ga_results {
 	const char* edit_bytes;
 	size_t n_trace;                         /* extent of `trace` */
 	const ga_trace_item_t* trace;
+	/* GA_F_OPS only (all three NULL / 0 without the flag): per read its operations as runs; `ops` has gaps like the arrays above */
+	const ga_read_ops_t* read_ops;          /* [n_reads] */
+	size_t n_ops;                           /* extent of `ops` */
+	const uint32_t* ops;                    /* a run: bits 0-2 the type, bits 3-31 the length (at least 1) */
 } ga_results_t;
 
 /* ---- alignment ----------------------------------------------------------------------------------------- */
-/* reads[i] owns seeds[seed_offsets[i] .. seed_offsets[i+1]).  flags: GA_F_TRACE fills TraceItem lists. */
+/* reads[i] owns seeds[seed_offsets[i] .. seed_offsets[i+1]).  flags: GA_F_TRACE fills TraceItem lists; GA_F_OPS fills read_ops / ops.
+ *
+ * GA_F_OPS: PER-BASE OPERATIONS, RUN-LENGTH CODED ON THE DEVICE.  THE RULE.  ops(read) is the sequence of the `type` fields of the read's
+ * TraceItem list -- exactly the list GA_F_TRACE returns (getTraceInfo, GraphAligner.h:690-780) --, types 1 MATCH, 2 MISMATCH, 3 INSERTION,
+ * 4 DELETION, 5 FORWARDBACKWARDSPLIT, taken in list order and cut into maximal runs of equal type.  A read with failed != 0 or status !=
+ * GA_S_OK has no runs.  A run is one uint32_t: bits 0-2 the type, bits 3-31 the length (at least 1).  The rule is defined by that list
+ * and by nothing else.
+ * What it means per extension job (one direction of one seed), whose traceback is a stream of moves from its start cell (last row) back
+ * to row 0.  Cells at rows >= the job's trace_rows are dropped (the first moves of the stream); K kept cells give K - 1 items, one per
+ * kept move, the first cell of a part has none.  A kept move leads from cell A (later, higher row) back to cell B.  A move left (same
+ * row) is a DELETION.  A move up (same column) is an INSERTION, unless the column is a node of length 1 that has itself as
+ * out-neighbour: the reference counts that step as a diagonal (:742).  A diagonal is a MATCH or a MISMATCH.  Forward job: the item
+ * describes A, the characters are seq[pos + row(A)] and the graph base at A.  Backward job: the final trace is the job's reversed and
+ * mirrored (reverseTrace, :3026-3037), so the item describes B's mirror cell: the characters are seq[pos - 1 - row(B)] and the base of
+ * the other strand's node at the offset counted from its end (the complement of the graph base at B, except in a graph with overlaps,
+ * whose strands are cut differently); its stream order is already the final order, a forward job's is its reverse.  The match test is characterMatch
+ * (:2039-2110: the read character's IUPAC set against the graph base); a cell on a dummy node matches nothing.  A read's list is the
+ * backward part, one SPLIT item when both parts have cells, the forward part; nothing merges across the SPLIT.
+ * Where they are made: by two kernels inside ga_batch_run, after the last pass, from the jobs' move bytes where they lie in HBM (a
+ * counting launch, a scan, a writing launch: no bound and no capacity miss); ga_batch_collect copies the winning seed's runs.  Two kinds
+ * of reads get their runs from the TraceItem list on the host instead, and are counted (ga_batch_ops_stats): a read with a character
+ * outside IUPAC, and a read whose forward part the reference does not shift by the seed's position although that is > 0 (:3091-3094).
+ * With GA_F_OPS the first pass hands back moves, not node runs, exactly as with GA_F_TRACE.  Without the flag nothing changes: no
+ * kernel more, no allocation more.  A back end that does not code operations refuses the prepare with GA_E_INVALID.  Memory kept
+ * with the graph from the first flagged batch on: the table of every node's mirror node, 4 bytes per node. */
 #define GA_F_TRACE 1u
+#define GA_F_OPS 2u
 int ga_align_batch(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_t* seeds, const size_t* seed_offsets,
                    int initial_bandwidth, int ramp_bandwidth, uint32_t flags, ga_results_t** out);
 void ga_results_free(ga_results_t* r);
@@ -199,6 +239,19 @@ typedef struct ga_batch_stats {
 	                                characters only) and the first-pass kernel handed back node runs instead of one byte per move */
 } ga_batch_stats_t;
 int ga_batch_stats(const ga_batch_t* b, ga_batch_stats_t* out);
+
+/* a batch prepared with GA_F_OPS (GA_E_INVALID otherwise): the two operations kernels of the last ga_batch_run and, from the last
+ * ga_batch_collect, where the reads' runs came from */
+typedef struct ga_batch_ops_stats {
+	double count_kernel_ms;      /* HIP-event time of the counting launch */
+	double write_kernel_ms;      /* ... of the writing launch */
+	uint64_t jobs_coded;         /* jobs with status ok, kept slices and move bytes */
+	uint64_t moves_read;         /* their moves */
+	uint64_t runs_written;       /* their runs */
+	uint64_t reads_from_device;  /* aligned reads whose runs are the kernels' */
+	uint64_t reads_from_host;    /* reads whose runs -- or whose GA_S_ASSERTION -- came from the TraceItem list on the host (see GA_F_OPS) */
+} ga_batch_ops_stats_t;
+int ga_batch_ops_stats(const ga_batch_t* b, ga_batch_ops_stats_t* out);
 
 /* ---- seeds found on the device ------------------------------------------------------------------------- */
 /* A k-mer index of the uploaded graph and, per batch of reads, up to max_seeds seeds per read in the form ga_align_batch takes.  The rule
