@@ -148,10 +148,8 @@ class AlignerParams:
         self.opsFile = ""           # --ops-out: per aligned read its operations (GA_F_OPS): counts, identity and the run string
 
 
-def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr, seed_lib_path=None):
-    """Aligner.cpp:230-322 with the per-read loop of :107-205.  Returns the list of (read name, result dict) written.
-    (seed_lib_path: tests only.  The host emulation comes as two libraries, one that aligns and one that finds seeds; with it the
-    graph is loaded a second time into the named library for --find-seeds.  The product library does both.)"""
+def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr):
+    """Aligner.cpp:230-322 with the per-read loop of :107-205.  Returns the list of (read name, result dict) written."""
     if not os.path.exists(params.fastqFile):
         err.write("No fastq file exists\n")
         raise SystemExit(0)
@@ -174,35 +172,32 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr,
         seeds_of = {i: seeds_by_name[r.seq_id] for i, r in enumerate(reads) if r.seq_id in seeds_by_name}
     graph = load_graph(params.graphFile, device=device, lib_path=lib_path)
     if find_seeds:
-        seeder = graph if seed_lib_path is None else load_graph(params.graphFile, device=device, lib_path=seed_lib_path)
         walks = getattr(params, "seedWalks", 0)
         coord = getattr(params, "seedCoord", "file")
-        st = seeder.build_seed_index(k=params.seedK, max_walks=walks, coordinate=coord)
+        st = graph.build_seed_index(k=params.seedK, max_walks=walks, coordinate=coord)
         line = "seed index: %d entries of %d k-mers (k %d), %.1f MB" % (st["entries"], st["kmers_seen"], st["k"], st["bytes"] / 1e6)
         if walks:
-            ws = seeder.seed_index_walk_stats()
+            ws = graph.seed_index_walk_stats()
             line += ", walks: %d of %d tail starts skipped (more than %d walks)" % (ws["tail_starts_skipped"], ws["tail_starts"], ws["max_walks"])
         out.write(line + "\n")
         if coord == "topology":
-            cs = seeder.seed_coord_stats()
+            cs = graph.seed_coord_stats()
             out.write("seed coordinate: topology, %d trees, %d cycles cut, %d + %d rounds\n" % (cs["trees"], cs["cycles_cut"], cs["cycle_rounds"], cs["depth_rounds"]))
         by_locus = getattr(params, "seedLoci", False)
         # seeds and job plan on the device from one upload of the reads (Graph.prepare_seeded), in the order the reads are aligned in;
         # a library or back end without that goes the two-call way
-        seeded = None
-        if seeder is graph:
-            try:
-                seeded = graph.prepare_seeded([r.sequence for r in reads[::-1]], dict(max_seeds=params.seedMax), by_locus,
-                                              params.initialBandwidth, params.rampBandwidth, flags=flags)
-            except binding.SeededUnsupported:
-                seeded = None
+        try:
+            seeded = graph.prepare_seeded([r.sequence for r in reads[::-1]], dict(max_seeds=params.seedMax), by_locus,
+                                          params.initialBandwidth, params.rampBandwidth, flags=flags)
+        except binding.SeededUnsupported:
+            seeded = None
         if seeded is not None:
             found = seeded.seeds()
             for field in ("seeds", "support", "n_hits", "truncated", "locus_hits", "locus_span", "n_loci"):     # (back into the reads' order)
                 if getattr(found, field) is not None:
                     setattr(found, field, getattr(found, field)[::-1])
         else:
-            found = seeder.find_seeds([r.sequence for r in reads], loci=by_locus, max_seeds=params.seedMax)
+            found = graph.find_seeds([r.sequence for r in reads], loci=by_locus, max_seeds=params.seedMax)
         seeds_of = {i: s for i, s in enumerate(found.seeds) if s}
         out.write("seeds found for %d of %d reads\n" % (len(seeds_of), len(reads)))
         if by_locus:

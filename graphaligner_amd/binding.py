@@ -118,7 +118,7 @@ class GaSeedSetLoci(C.Structure):
                                      ("locus_last_p", C.POINTER(C.c_uint32)), ("n_loci", C.POINTER(C.c_uint32))]
 
 
-# the seeding entry points: in the product library and in tests/_build/libga_seed_emul.so, not in the alignment-only emulation
+# the seeding entry points, in the product library and in the host emulation (tests/_build/libga_emul.so)
 SEED_EXPORTS = ["ga_seed_params_default", "ga_graph_build_seed_index", "ga_graph_seed_index_stats", "ga_graph_seed_index_copy", "ga_find_seeds",
                 "ga_seed_set_free", "ga_graph_build_seed_index_walks", "ga_graph_seed_index_walk_stats", "ga_find_seeds_loci",
                 "ga_graph_set_seed_coordinate", "ga_graph_seed_coord_stats", "ga_graph_seed_coordinate_copy"]

@@ -1,8 +1,8 @@
 // ga_backend.h -- the seam between the host library (graph model, job building, result
 // assembly: ga_host.cpp) and whatever executes the extension program.  The product links
-// ga_device.hip (gfx950, HIP).  tests/emul/ links a host emulation of the same program so the
+// ga_device.hip (gfx950, HIP).  tests/emul/ links a host emulation of the same programs so the
 // device logic can be checked in the CPU-only container; that object is never part of the
-// shipped library.
+// shipped library.  (It can withhold a capability, tests/emul/ga_emul.h: it then answers with the defaults of the classes below.)
 #pragma once
 #if defined(__SSE2__)
 #include <emmintrin.h>
@@ -166,10 +166,10 @@ public:
 	// first half of a seeded batch: upload, seeding, plan, match words (where the back end builds them), download.  The batch it returns
 	// runs once finishSeeded has been given the host's copy of the jobs.  A back end without the feature refuses (100 = GA_E_INVALID)
 	virtual GaBackendBatch* beginSeededBatch(const GaSeededRequest&, GaSeededPlan&, int* status) { *status = 100; return nullptr; }
-	// nullptr: this back end has no seeding (the alignment-only host emulation of tests/emul)
+	// nullptr: this back end has no seeding (the host emulation of tests/emul with seeding withheld)
 	virtual GaSeedEngine* seedEngine() { return nullptr; }
 	// true: ga_backend_create_batch wants a GaEqSource and builds the match words on its side (the product: a kernel over the uploaded
-	// reads); false: it wants the finished words (the host emulation of tests/emul)
+	// reads); false: it wants the finished words (the host emulation of tests/emul with its own words withheld)
 	virtual bool buildsMatchWords() const { return false; }
 	// true: this back end codes operations (GaRunConfig::emit_ops); on one that does not, a prepare with GA_F_OPS is refused
 	virtual bool codesOps() const { return false; }

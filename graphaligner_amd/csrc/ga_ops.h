@@ -7,7 +7,7 @@
 // inside GAO_LANES(l) { ... } every lane runs the block for its own l; lanes exchange values only through the OpsLds block with a
 // sync() between the phase that writes and the phase that reads, and through the two wave primitives below (scan, ballot).  Everything
 // declared outside a lane block is the same in every lane, so the control flow around the blocks is uniform.  On gfx950 a lane block
-// is straight-line code of the lane; in the host build of the tests (tests/emul_ops) it is a loop over the 64 lanes.
+// is straight-line code of the lane; in the host build of the tests (tests/emul) it is a loop over the 64 lanes.
 //
 // The same program runs twice: a counting launch leaves one run count per job, an exclusive scan turns the counts into places, and a
 // writing launch stores the runs there -- a backward job's in stream order, a forward job's back to front, which is the final order

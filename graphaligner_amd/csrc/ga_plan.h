@@ -4,7 +4,7 @@
 // job, and after two exclusive scans over the slots the GaJob, GaEqFill and GaPlanSeed records at their places.
 //
 // One function per launch and item, as in ga_seed.h: on gfx950 a kernel of ga_device.hip calls it for its wave or lane, the host build of
-// tests/emul_seed_plan calls it for every item in turn.  Every loop is counted; no item waits for another.
+// tests/emul calls it for every item in turn.  Every loop is counted; no item waits for another.
 #pragma once
 #include "ga_backend.h"
 #include "ga_seed.h"

@@ -5,7 +5,7 @@
 // every lane runs the block for its own l, and lanes exchange values only through the SeedLds block (LDS) or the wave's hit buffer
 // (HBM) with a wave_sync() between the phase that writes and the phase that reads; everything declared outside a lane block is the
 // same in every lane (it is derived from such exchanged values), so the control flow around the blocks is uniform.  On gfx950 a lane
-// block is straight-line code of the lane; in the host build of the tests (tests/emul_seed) it is a loop over the 64 lanes, which is
+// block is straight-line code of the lane; in the host build of the tests (tests/emul) it is a loop over the 64 lanes, which is
 // the same program because of that discipline.  The one wave primitive that is not a lane block is the exclusive scan of the tile's
 // hit counts (cross-lane DPP/permute moves on the device, a running sum on the host).
 //

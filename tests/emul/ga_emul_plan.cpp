@@ -1,29 +1,16 @@
-// ga_backend_seed_plan_emul.cpp -- TEST-ONLY back end for seeded batches (ga_batch_prepare_seeded): the newest seeding emulation
-// (tests/emul_seed_coord) and the newest alignment emulation (tests/emul_wide_sparse), both compiled into this file as they are, and
-// between them the plan program of graphaligner_amd/csrc/ga_plan.h run on the host launch by launch: first_bad_lane for the 64 lanes of
+// ga_emul_plan.cpp -- TEST-ONLY (ga_emul.h): the first half of a seeded batch (ga_batch_prepare_seeded).  The seed engine finds the
+// seeds, then the plan program of graphaligner_amd/csrc/ga_plan.h runs on the host launch by launch: first_bad_lane for the 64 lanes of
 // every read's wave and their minimum, plan_slot for every slot, the two scans as running sums (what replaces the device library's
-// scans here), plan_write for every slot and plan_tail.  The work arrays are filled with a pattern before use.  The older host builds
-// stay as they are and refuse ga_batch_prepare_seeded; this one carries it end to end.
-// Linked only into tests/_build/libga_seed_plan_emul.so, next to the product's host code (ga_host.cpp, ga_vgio.cpp, ga_seed_host.cpp).
-#include "../../graphaligner_amd/csrc/ga_backend.h"
+// scans here), plan_write for every slot and plan_tail; then the match words from the plan's fills, unless they are withheld.  The
+// work arrays and the download's block are filled with a pattern before use.
+#include <algorithm>
+#include <chrono>
+#include <cstring>
 
-// the two older back ends under names of their own: this file's ga_backend_upload_graph / ga_backend_create_batch put them together
-#define ga_backend_upload_graph ga_seed_part_upload_graph
-#define ga_backend_create_batch ga_seed_part_create_batch
-#include "../emul_seed_coord/ga_backend_seed_coord_emul.cpp"
-#undef ga_backend_upload_graph
-#undef ga_backend_create_batch
-#define ga_backend_upload_graph ga_align_part_upload_graph
-#define ga_backend_create_batch ga_align_part_create_batch
-#include "../emul_wide_sparse/ga_backend_wide_sparse_emul.cpp"
-#undef ga_backend_upload_graph
-#undef ga_backend_create_batch
-
+#include "ga_emul.h"
 #include "../../graphaligner_amd/csrc/ga_plan.h"
 
-GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& g, const GaHmmTables& hmm, int device, int* status);
-GaBackendBatch* ga_backend_create_batch(GaBackendGraph* g, GaRowsProvider rows, const uint64_t* eq, const GaEqSource* src, size_t eqWords, const std::vector<GaJob>& jobs,
-                                        const GaRunConfig& cfg, int* status);
+using namespace gae;
 
 namespace {
 
@@ -62,33 +49,11 @@ struct PlanArrays
 	}
 };
 
-struct PlanGraph : GaBackendGraph
-{
-	GaFlatGraph flat;
-	std::unique_ptr<GaBackendGraph> seedPart, alignPart;
-	GaSeedEngine* seedEngine() override { return seedPart->seedEngine(); }
-	GaBackendBatch* beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status) override;
-};
+}  // namespace
 
-struct PlanBatch : GaBackendBatch
+GaBackendBatch* EmulGraph::beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status)
 {
-	PlanGraph* g = nullptr;
-	std::unique_ptr<GaBackendBatch> inner;
-	int finishSeeded(const std::vector<GaJob>& jobs, const GaRunConfig& cfg, GaRowsProvider rows, const uint64_t* eq, size_t eqWords) override
-	{
-		int st = 0;
-		inner.reset(ga_align_part_create_batch(g->alignPart.get(), rows, eq, nullptr, eqWords, jobs, cfg, &st));
-		return inner ? 0 : (st ? st : 102);
-	}
-	bool emittingRuns() const override { return inner && inner->emittingRuns(); }
-	int run() override { return inner ? inner->run() : 100; }
-	int fetch(std::vector<GaJobOut>& outs, const uint8_t** traceBytes, uint64_t* nBytes) override { return inner ? inner->fetch(outs, traceBytes, nBytes) : 100; }
-	void fetchDone() override { if (inner) inner->fetchDone(); }
-	GaRunStats stats() const override { return inner ? inner->stats() : GaRunStats(); }
-};
-
-GaBackendBatch* PlanGraph::beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status)
-{
+	if (without & NO_SEEDED) return GaBackendGraph::beginSeededBatch(req, plan, status);
 	GaSeedEngine* eng = seedEngine();
 	if (!eng || !eng->built()) { *status = 100; return nullptr; }
 	const size_t nReads = req.nReads, nSlots = nReads * req.p.max_seeds;
@@ -135,29 +100,22 @@ GaBackendBatch* PlanGraph::beginSeededBatch(const GaSeededRequest& req, GaSeeded
 	plan.seed_ms = so.kernel_ms;
 	plan.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	if (plan.rowsTotal > req.rowsBound) { *status = 102; return nullptr; }
-	PlanBatch* b = new PlanBatch();
+	EmulBatch* b = new EmulBatch();
 	b->g = this;
+	b->seeded = true;
+	if (buildsMatchWords())
+	{
+		// the match words from the fills as the plan left them (ga_eq_words_planned_kernel)
+		GaEqSource src;
+		src.seq = req.block; src.seqBytes = req.blockBytes;
+		src.fills = L.fills; src.nFills = plan.nJobs;
+		src.rowCode = req.rowCode; src.rowCodeRc = req.rowCodeRc; src.padCode = req.padCode;
+		src.twin = req.twin;
+		b->buildWords(src, (size_t)(plan.rowsTotal / 64 + 1) * 5);
+		plan.badFills = b->bad.data();
+	}
 	*status = 0;
 	return b;
-}
-
-}  // namespace
-
-GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& flat, const GaHmmTables& hmm, int device, int* status)
-{
-	PlanGraph* g = new PlanGraph();
-	g->flat = flat;
-	g->seedPart.reset(ga_seed_part_upload_graph(flat, hmm, device, status));
-	g->alignPart.reset(ga_align_part_upload_graph(flat, hmm, device, status));
-	if (!g->seedPart || !g->alignPart) { delete g; if (!*status) *status = 102; return nullptr; }
-	*status = 0;
-	return g;
-}
-
-GaBackendBatch* ga_backend_create_batch(GaBackendGraph* g, GaRowsProvider rows, const uint64_t* eq, const GaEqSource* src, size_t eqWords, const std::vector<GaJob>& jobs,
-                                        const GaRunConfig& cfg, int* status)
-{
-	return ga_align_part_create_batch(static_cast<PlanGraph*>(g)->alignPart.get(), rows, eq, src, eqWords, jobs, cfg, status);
 }
 
 // component hook: the layout step (slot_sizes, the two scans, plan_write, plan_tail) over fabricated job sizes, no sequences: per slot the

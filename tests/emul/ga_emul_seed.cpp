@@ -1,20 +1,17 @@
-// ga_backend_seed_loci_emul.cpp -- TEST-ONLY back end for the seeding program (graphaligner_amd/csrc/ga_seed.h) with both index
-// builds and both lookups: seeds hit by hit (find) and one seed per locus (findLoci).  tests/emul_seed and tests/emul_seed_walks, which
-// the older tests pin, stay as they are; this file repeats the latter and adds findLoci.  Everything runs on the host, one wave after
-// the other, a wave's lane blocks as loops over its 64 lanes (GA_EMULATE) and the wave primitives of tests/emul/ga_wave_emul.h.
-// Linked only into tests/_build/libga_seed_loci_emul.so, next to the product's host code (ga_host.cpp, ga_vgio.cpp, ga_seed_host.cpp).
-// This library does not align: ga_backend_create_batch refuses, and the tests that align use tests/_build/libga_emul.so for that.
-// What replaces device-library calls here: the stable radix sort of the index entries (std::stable_sort by key), the scan of the
-// per-node counts and the scan of the "first of its kind" flags.  A wave slot's buffers, the per-hit ones of findLoci included, are
-// filled with a pattern before the call and reused from read to read with whatever the read before left in them.
-#define GA_EMULATE 1
+// ga_emul_seed.cpp -- TEST-ONLY (ga_emul.h): the seed engine of the host emulation, the seeding program of graphaligner_amd/csrc/ga_seed.h
+// with both index builds (build, buildWalks), both lookups (find, findLoci) and the topology coordinate (setCoordinate): the per-node and
+// per-wave functions of ga_seed.h run for every item in turn, launch by launch, with the two buffers, the "still moving" words and the
+// bounds on the rounds that ga_seed_dev.h uses.  What replaces device-library calls here: the stable radix sort of the index entries
+// (std::stable_sort by key) and the three scans (per-node counts, "first of its kind" flags, the trees' extents).  A wave slot's
+// buffers and the coordinate's work buffers are filled with a pattern before use.
+// GA_EMUL_WITHOUT=walks,loci,topology: the withheld entry points answer as GaSeedEngine's defaults do.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
 #include <numeric>
 
-#include "../../graphaligner_amd/csrc/ga_backend.h"
+#include "ga_emul.h"
 #include "../../graphaligner_amd/csrc/ga_seed.h"
 
 namespace {
@@ -24,19 +21,22 @@ struct EmulSeedEngine : GaSeedEngine
 	const GaDevGraph* g;
 	std::vector<uint64_t> keys, vals;
 	std::vector<uint32_t> dir;
-	std::vector<int64_t> linx;
+	std::vector<int64_t> linx, linxFile;
+	GaSeedCoordInfo cinf;
 	gas::SeedIndex ix{};
 	GaSeedIndexInfo inf;
 	GaSeedWalkInfo winf;
 	bool have = false;
-	explicit EmulSeedEngine(const GaDevGraph* graph) : g(graph) {}
+	const uint32_t without;
+	EmulSeedEngine(const GaDevGraph* graph, uint32_t withheld) : g(graph), without(withheld) {}
 	bool built() const override { return have; }
 	GaSeedIndexInfo info() const override { return inf; }
 
-	GaSeedWalkInfo walkInfo() const override { return winf; }
+	GaSeedWalkInfo walkInfo() const override { return (without & gae::NO_WALKS) ? GaSeedEngine::walkInfo() : winf; }
 	int build(uint32_t k, uint32_t sampleShift, const std::vector<int64_t>& lx) override { return buildIndex(k, sampleShift, 0, lx); }
 	int buildWalks(uint32_t k, uint32_t sampleShift, uint32_t maxWalks, const std::vector<int64_t>& lx) override
 	{
+		if (without & gae::NO_WALKS) return GaSeedEngine::buildWalks(k, sampleShift, maxWalks, lx);
 		if (maxWalks < 1 || maxWalks > 256 || k - 1 > gas::kWalkLevels) return 100;
 		return buildIndex(k, sampleShift, maxWalks, lx);
 	}
@@ -94,6 +94,8 @@ struct EmulSeedEngine : GaSeedEngine
 			if (i < n && (i == 0 || keys[i] != keys[i - 1])) distinct++;
 		}
 		linx = lx;
+		linxFile = lx;
+		cinf = GaSeedCoordInfo();
 		ix.k = k; ix.sample_shift = sampleShift; ix.dir_shift = 2 * k - bits; ix.n_entries = n;
 		ix.keys = keys.data(); ix.vals = vals.data(); ix.dir = dir.data(); ix.linx = linx.data();
 		inf = GaSeedIndexInfo();
@@ -102,6 +104,79 @@ struct EmulSeedEngine : GaSeedEngine
 		inf.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 		winf = w;
 		have = true;
+		return 0;
+	}
+
+	GaSeedCoordInfo coordInfo() const override { return (without & gae::NO_TOPOLOGY) ? GaSeedEngine::coordInfo() : cinf; }
+	int copyLin(int64_t* lin, size_t capacity) const override
+	{
+		if (without & gae::NO_TOPOLOGY) return GaSeedEngine::copyLin(lin, capacity);
+		if (!have) return 100;
+		const size_t n = std::min<size_t>(capacity, linx.size());
+		for (size_t i = 0; i < n; i++) lin[i] = linx[i] >> 1;
+		return 0;
+	}
+
+	// the launches of DevSeedEngine::setCoordinate, a launch = a loop over the nodes
+	int setCoordinate(int kind, GaSeedCoordInfo& out) override
+	{
+		if (without & gae::NO_TOPOLOGY) return GaSeedEngine::setCoordinate(kind, out);
+		if (!have || (kind != 0 && kind != 1)) return 100;
+		if (kind == 0)
+		{
+			std::copy(linxFile.begin(), linxFile.end(), linx.begin());         // (in place: ix.linx points at it)
+			cinf = GaSeedCoordInfo();
+			out = cinf;
+			return 0;
+		}
+		const auto t0 = std::chrono::steady_clock::now();
+		const uint32_t n = g->n_nodes, R = gas::coord_rounds(n);
+		std::vector<gas::CoordDepth> stA(n), stB(n);
+		memset(stA.data(), 0xa5, (size_t)n * sizeof(gas::CoordDepth));
+		memset(stB.data(), 0xa5, (size_t)n * sizeof(gas::CoordDepth));
+		std::vector<uint32_t> par(n, 0xa5a5a5a5u), parLen(n, 0xa5a5a5a5u), mark(n, 0);
+		std::vector<uint64_t> ext(n, 0), contrib((size_t)n + 1, 0xa5a5a5a5a5a5a5a5ull), base((size_t)n + 1, 0xa5a5a5a5a5a5a5a5ull);
+		GaSeedCoordInfo c;
+		c.kind = 1;
+		std::vector<gas::CoordCyc> cyA(n), cyB(n);                           // (the device keeps these in the first half of the two state buffers)
+		memset(cyA.data(), 0xa5, (size_t)n * sizeof(gas::CoordCyc));
+		memset(cyB.data(), 0xa5, (size_t)n * sizeof(gas::CoordCyc));
+		gas::CoordCyc* ca = cyA.data(); gas::CoordCyc* co = cyB.data();
+		bool mv = false;
+		for (uint32_t v = 0; v < n; v++) { gas::coord_parent(*g, v, par.data(), parLen.data()); mv |= gas::coord_cyc_init(par.data(), v, ca); }
+		while (mv && c.cycle_rounds < R)
+		{
+			mv = false;
+			for (uint32_t v = 0; v < n; v++) mv |= gas::coord_cyc_round(ca, co, v);
+			c.cycle_rounds++;
+			std::swap(ca, co);
+		}
+		if (mv)
+		{
+			for (uint32_t v = 0; v < n; v++) gas::coord_mark(ca, mark.data(), v);
+			for (uint32_t v = 0; v < n; v++) c.cycles_cut += gas::coord_cut(ca, mark.data(), par.data(), v) ? 1u : 0u;
+		}
+		gas::CoordDepth* da = stA.data(); gas::CoordDepth* dd = stB.data();
+		mv = false;
+		for (uint32_t v = 0; v < n; v++) mv |= gas::coord_depth_init(par.data(), parLen.data(), v, da);
+		while (mv && c.depth_rounds < R + 1)
+		{
+			mv = false;
+			for (uint32_t v = 0; v < n; v++) mv |= gas::coord_depth_round(da, dd, v);
+			c.depth_rounds++;
+			std::swap(da, dd);
+		}
+		if (mv) return 102;
+		for (uint32_t v = 0; v < n; v++) gas::coord_extent(*g, da, ext.data(), v);
+		for (uint32_t v = 0; v < n; v++) c.trees += gas::coord_contrib(*g, da, ext.data(), contrib.data(), v) ? 1u : 0u;
+		contrib[n] = 0;
+		uint64_t run = 0;
+		for (uint32_t v = 0; v <= n; v++) { base[v] = run; run += contrib[v]; }
+		for (uint32_t v = 0; v < n; v++) gas::coord_write(*g, da, base.data(), linx.data(), v);
+		c.extent_sum = base[n] - (uint64_t)c.trees * (uint64_t)gas::kTreeGap;
+		c.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		cinf = c;
+		out = c;
 		return 0;
 	}
 
@@ -114,7 +189,10 @@ struct EmulSeedEngine : GaSeedEngine
 	}
 
 	int find(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override { return run(seqs, lens, nReads, p, out, false); }
-	int findLoci(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override { return run(seqs, lens, nReads, p, out, true); }
+	int findLoci(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out) override
+	{
+		return (without & gae::NO_LOCI) ? GaSeedEngine::findLoci(seqs, lens, nReads, p, out) : run(seqs, lens, nReads, p, out, true);
+	}
 
 	int run(const char* const* seqs, const size_t* lens, size_t nReads, const GaSeedParams& p, GaSeedOut& out, bool byLocus)
 	{
@@ -180,39 +258,6 @@ struct EmulSeedEngine : GaSeedEngine
 	}
 };
 
-struct EmulSeedGraph : GaBackendGraph
-{
-	GaFlatGraph flat;
-	std::vector<uint32_t> nodeRec;
-	GaDevGraph dev;
-	std::unique_ptr<EmulSeedEngine> seed;
-	GaSeedEngine* seedEngine() override { return seed.get(); }
-};
-
 }  // namespace
 
-GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& flat, const GaHmmTables&, int, int* status)
-{
-	EmulSeedGraph* g = new EmulSeedGraph();
-	g->flat = flat;
-	g->dev.n_nodes = (uint32_t)(flat.node_start.size() - 1);
-	g->dev.reserved = 0;
-	g->dev.node_start = g->flat.node_start.data();
-	g->dev.seq2 = g->flat.seq2.data();
-	g->dev.in_off = g->flat.in_off.data();
-	g->dev.in_nbr = g->flat.in_nbr.data();
-	g->dev.out_off = g->flat.out_off.data();
-	g->dev.out_nbr = g->flat.out_nbr.data();
-	g->nodeRec = ga_build_node_records(g->flat);
-	g->dev.node_rec = g->nodeRec.data();
-	g->seed = std::make_unique<EmulSeedEngine>(&g->dev);
-	*status = 0;
-	return g;
-}
-
-// this library finds seeds; it does not align (100 = GA_E_INVALID)
-GaBackendBatch* ga_backend_create_batch(GaBackendGraph*, GaRowsProvider, const uint64_t*, const GaEqSource*, size_t, const std::vector<GaJob>&, const GaRunConfig&, int* status)
-{
-	*status = 100;
-	return nullptr;
-}
+GaSeedEngine* gae::newSeedEngine(const GaDevGraph* g, uint32_t without) { return new EmulSeedEngine(g, without); }

@@ -1,9 +1,7 @@
-"""Cases for GA_F_OPS shared by tests/test_ops.py (host build of the operations program, tests/emul_ops) and tests/test_ops_gpu.py (the
+"""Cases for GA_F_OPS shared by tests/test_ops.py (host build of the operations program, tests/emul) and tests/test_ops_gpu.py (the
 product on the GPU).  Everywhere the expected value is ops_model.rle(oracle trace types): the oracle's TraceItem list through
 oracle_binding, cut into runs by ops_model.  The oracle's results are computed once per process (parity_common's memo) and left unchanged."""
-import os
 import random
-import subprocess
 
 import numpy as np
 
@@ -15,14 +13,7 @@ import parity_cases as pcases
 import parity_common as pc
 import wide_cases as wc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPS_SO = os.path.join(ROOT, "tests", "_build", "libga_ops_emul.so")
 F_OPS = binding.GA_F_OPS
-
-
-def ops_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_ops")])
-    return OPS_SO
 
 
 def run_ops(nodes, edges, reads, seeds, bw, ramp=0, overlap=0, lib_path=None, flags=F_OPS, gfa=None):
@@ -339,3 +330,18 @@ def case_flag_changes_nothing_else(lib_path=None):
     stats = binding.GaBatchOpsStats()
     assert b.L.ga_batch_ops_stats(b.h, C.byref(stats)) == 100
     return st
+
+
+# ---- a seeded batch against the two calls ----------------------------------------------------------------------------------------------
+def case_seeded_batch_equals_two_calls(g, reads, min_aligned, lib_path=None):
+    """align_reads(..., flags=GA_F_OPS) equals prepare(reads, find_seeds(reads)) with the flag, run for run, and both the oracle"""
+    gg = binding.Graph(g.nodes, g.edges, lib_path=lib_path)
+    gg.build_seed_index()
+    one = gg.align_reads(reads, flags=binding.GA_F_OPS)
+    found = gg.find_seeds(reads)
+    two = gg.align(reads, found.seeds, 35, 0, binding.GA_F_OPS)
+    oras = pc.oracle_results(g.nodes, g.edges, reads, [list(s) for s in found.seeds], 35)
+    aligned = compare_ops(one, oras, "seeded batch")
+    assert aligned >= min_aligned, aligned
+    for a, b in zip(one, two):
+        assert om.as_pairs(a["ops"]) == om.as_pairs(b["ops"]) and a["op_counts"] == b["op_counts"]

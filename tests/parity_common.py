@@ -1,6 +1,7 @@
 """shared helpers for the parity tests: run the same reads through the C ABI (real GPU library
 or the host emulation of the device program) and through the CPU oracle, then compare every
 field the reference's AlignmentResult carries."""
+import contextlib
 import os
 import subprocess
 
@@ -17,8 +18,39 @@ _STATUS_MAP = {0: 0, 1: 1, 2: 2, 3: 3}
 
 
 def emul_lib_path():
+    """the one host emulation (tests/emul): with nothing set it does what the product's back end does"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul")])
     return EMUL_SO
+
+
+# GA_EMUL_WITHOUT (tests/emul/ga_emul.h) for the capability sets that the tests name: what the back ends of earlier stages of the
+# project lacked.  A graph uploaded under a profile answers with the interface's defaults for what it withholds, which is what the
+# tests of the host code's refusals, of the host-built tables and of one ladder against another need.
+PROFILES = {
+    "emul": "wide,wide_sparse,words,ops,seeding",                # the ladder up to <256,true,true>, words from the host, no seeding
+    "emul_wide": "wide_sparse,words,ops,seeding",                # ... with <4096,true>
+    "emul_wide_sparse": "words,ops,seeding",                     # ... and <4096,true,true>
+    "emul_seed": "walks,loci,topology,seeded",                   # build and find only
+    "emul_seed_walks": "loci,topology,seeded",                   # ... with buildWalks
+    "emul_seed_loci": "topology,seeded",                         # ... and findLoci
+    "emul_seed_coord": "seeded",                                 # ... and setCoordinate: everything but seeded batches (the two-call path)
+    "emul_seed_plan": "words,ops",                               # seeded batches over words from the host, no GA_F_OPS
+    "emul_ops": "seeding",                                       # GA_F_OPS over the back end's own words, no seeding
+}
+
+
+@contextlib.contextmanager
+def emul_profile(name):
+    """graphs uploaded inside the block withhold what PROFILES[name] lists (the switch is read at every upload)"""
+    before = os.environ.get("GA_EMUL_WITHOUT")
+    os.environ["GA_EMUL_WITHOUT"] = PROFILES[name]
+    try:
+        yield
+    finally:
+        if before is None:
+            del os.environ["GA_EMUL_WITHOUT"]
+        else:
+            os.environ["GA_EMUL_WITHOUT"] = before
 
 
 def compare_read(dev, ora, ctx=""):

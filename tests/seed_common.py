@@ -3,7 +3,6 @@ model of tests/seed_model.py, and the accuracy run (reads aligned from their tru
 the library finds, both judged against the simulation's truth by the reference's 0.7 rule)."""
 import json
 import os
-import subprocess
 
 import numpy as np
 
@@ -11,12 +10,6 @@ from graphaligner_amd import binding, compare, synth
 import seed_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED_EMUL_SO = os.path.join(ROOT, "tests", "_build", "libga_seed_emul.so")
-
-
-def seed_emul_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_seed")])
-    return SEED_EMUL_SO
 
 
 def big_node_graph(n=100000, seed=9):

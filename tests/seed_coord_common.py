@@ -3,23 +3,14 @@ product library): the host build, graphs with their node list permuted, the hand
 ga_graph_set_seed_coordinate with the model of tests/seed_coord_model.py, and the accuracy run of seed_common.accuracy with the
 coordinate set."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 
 from graphaligner_amd import binding, compare, synth
 import seed_coord_model as scm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED_COORD_EMUL_SO = os.path.join(ROOT, "tests", "_build", "libga_seed_coord_emul.so")
 STAT_KEYS = ("kind", "trees", "cycles_cut", "cycle_rounds", "depth_rounds", "extent_sum")
-
-
-def seed_coord_emul_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_seed_coord")])
-    return SEED_COORD_EMUL_SO
 
 
 def shuffled(nodes, seed=1):

@@ -1,22 +1,13 @@
 """shared helpers of the seeds-per-locus tests (tests/test_seed_loci.py on the host build, tests/test_seed_loci_gpu.py on the product
 library): the host build, the comparison of Graph.find_seeds(loci=True) with the model of tests/seed_loci_model.py, the hand-made
 cases of the rule (zigzag, gap, repeat) and the accuracy run of seed_common.accuracy with grouped seeds."""
-import os
-import subprocess
 
 import numpy as np
 
 from graphaligner_amd import binding, compare, synth
 import seed_loci_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED_LOCI_EMUL_SO = os.path.join(ROOT, "tests", "_build", "libga_seed_loci_emul.so")
 PARAM_SETS = (dict(), dict(max_seeds=1), dict(max_seeds=3), dict(max_hits=16), dict(min_support=1, window=100, diag_tol=5), dict(max_occ=1))
-
-
-def seed_loci_emul_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_seed_loci")])
-    return SEED_LOCI_EMUL_SO
 
 
 def as_dict(res, i):

@@ -1,23 +1,14 @@
-"""shared helpers of the seeded-batch tests (tests/test_seed_plan.py on the host build of tests/emul_seed_plan, tests/test_seed_plan_gpu.py
+"""shared helpers of the seeded-batch tests (tests/test_seed_plan.py on the host build of tests/emul, tests/test_seed_plan_gpu.py
 on the product library): the host build, graphs made of digraph nodes, the three-way comparison of a seeded batch's plan with the
 two-call path's and the model's, and the hand-made inputs for the clauses of the rule."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from graphaligner_amd import binding, synth
 import seed_plan_model as spm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED_PLAN_EMUL_SO = os.path.join(ROOT, "tests", "_build", "libga_seed_plan_emul.so")
 COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
-
-
-def seed_plan_emul_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_seed_plan")])
-    return SEED_PLAN_EMUL_SO
 
 
 def revcomp(s):

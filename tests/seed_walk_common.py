@@ -1,21 +1,11 @@
 """shared helpers of the walk-index tests (tests/test_seed_walks.py on the host build, tests/test_seed_walks_gpu.py on the product
 library): the graphs, the comparison of a library's walk index with the model of tests/seed_walk_model.py, and the accuracy run of
 seed_common.accuracy with a walk index (that function builds its index without arguments, hence the variant here)."""
-import os
-import subprocess
 
 import numpy as np
 
 from graphaligner_amd import binding, compare, synth
 import seed_walk_model
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED_WALKS_EMUL_SO = os.path.join(ROOT, "tests", "_build", "libga_seed_walks_emul.so")
-
-
-def seed_walks_emul_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_seed_walks")])
-    return SEED_WALKS_EMUL_SO
 
 
 GRAPHS = {

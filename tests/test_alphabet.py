@@ -1,8 +1,9 @@
 """The read alphabet on the host: alphabet_model.py (the rule as the reference's text states it) against the oracle, and the probe
 sets of alphabet_cases.py through the host emulation of the device program.
 
-The emulation ignores GaEqSource, so what runs here are the two host restatements of the rule: the match-word builder of
-ga_batch_prepare feeds the lanes = reads program, buildRows feeds the wave-per-read ladder.  GA_LANES chooses the first pass of the
+The emulation runs here with its own match words withheld (profile "emul" of parity_common.PROFILES: it takes the finished words and
+ignores GaEqSource), so what runs are the two host restatements of the rule: the match-word builder of ga_batch_prepare feeds the
+lanes = reads program, buildRows feeds the wave-per-read ladder.  GA_LANES chooses the first pass of the
 product; the emulation's name for the same choice is GA_EMUL_NO_LANES, and the fixture sets both, so that with the ladder first
 every job takes its rows from buildRows.  The kernel's own statement of the rule is test_alphabet_gpu.py's.
 """
@@ -18,6 +19,12 @@ GRAPH = pytest.mark.parametrize("name", sorted(ac.GRAPHS))
 @pytest.fixture(scope="module")
 def lib():
     return pc.emul_lib_path()
+
+
+@pytest.fixture(autouse=True)
+def host_built_tables(monkeypatch):
+    """every graph of this module is uploaded with the back end's own match words withheld: the tables under test are the host's"""
+    monkeypatch.setenv("GA_EMUL_WITHOUT", pc.PROFILES["emul"])
 
 
 def test_model_tables():

@@ -1,6 +1,6 @@
 """ga_find_seeds against the model of tests/seed_model.py (seeds, support, hit count, truncation, for every read), its determinism,
 the usability of the seeds (reads aligned from them against reads aligned from their true seeds) and the driver's --find-seeds.
-CPU: the seeding program built for the host (tests/emul_seed); alignment through the host emulation of tests/emul."""
+CPU: the seeding program and the alignment programs built for the host (tests/emul)."""
 import io
 import os
 import sys
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def world():
-    lib = sc.seed_emul_lib_path()
+    lib = pc.emul_lib_path()
     g = synth.bubble_graph(30000, node_len=32, seed=3)
     G = binding.Graph(g.nodes, g.edges, lib_path=lib)
     G.build_seed_index()
@@ -45,7 +45,7 @@ def test_seeds_equal_the_model(world):
 
 
 def test_other_k_and_sampling():
-    lib = sc.seed_emul_lib_path()
+    lib = pc.emul_lib_path()
     g = synth.linear_graph(20000)
     reads = sc.spiked_reads(g, seed=11)
     for k, s in ((11, 0), (31, 3), (21, 5)):
@@ -56,7 +56,7 @@ def test_other_k_and_sampling():
 
 def test_repeats_are_filtered():
     """a poly-A read against a graph with a long poly-A node and max_occ = 1: every k-mer of the read has many entries, nothing is used"""
-    lib = sc.seed_emul_lib_path()
+    lib = pc.emul_lib_path()
     base = synth.random_genome(3000, 8).tobytes().decode()
     nodes = [(1, base[:1500]), (2, "A" * 600), (3, base[1500:])]
     edges = [(1, False, 2, False), (2, False, 3, False)]
@@ -90,7 +90,7 @@ def test_seeds_are_usable():
     g = synth.bubble_graph(40000, node_len=32, seed=11)
     truth = []
     reads, seeds = synth.simulate_reads(g, 100, 3000, seed=5, truth=truth)
-    row = sc.accuracy(g, reads, seeds, truth, pc.emul_lib_path(), sc.seed_emul_lib_path())
+    row = sc.accuracy(g, reads, seeds, truth, pc.emul_lib_path(), pc.emul_lib_path())
     row.pop("seed_kernel_ms")
     print("seed accuracy (host emulation):", row)
     sc.record("seed_accuracy_cpu.json", "bubble_graph(40000, node_len=32, seed=11), 100 x 3000 bp, seed=5", row)
@@ -98,7 +98,7 @@ def test_seeds_are_usable():
     assert row["good_true_seeds"] >= 90, row
 
 
-def test_driver_finds_its_own_seeds(tmp_path):
+def test_driver_finds_its_own_seeds(tmp_path, monkeypatch):
     """--find-seeds on files of the kind test_aligner_driver writes: the GAM's alignments pass the 0.7 rule against the truth; without
     the option the old message still comes"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -123,7 +123,8 @@ def test_driver_finds_its_own_seeds(tmp_path):
     assert p.findSeeds and p.seedK == 15 and p.seedMax == 2
     p.outputDir = str(tmp_path)
     out, err = io.StringIO(), io.StringIO()
-    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err, seed_lib_path=sc.seed_emul_lib_path())
+    monkeypatch.setenv("GA_EMUL_WITHOUT", "seeded")            # the two-call path: prepare_seeded is refused, find_seeds and prepare follow
+    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err)
     for n in ("short", "orphan"):
         assert "read %s has no seed hits" % n in out.getvalue() and "read %s has no seed hits" % n in err.getvalue()
     got = _decode_gam(str(tmp_path / "out.gam"))

@@ -1,4 +1,4 @@
-"""GA_F_OPS on the host build (tests/emul_ops: the alignment emulation of tests/emul_wide_sparse and graphaligner_amd/csrc/ga_ops.h run
+"""GA_F_OPS on the host build (tests/emul: behind the emulated ladder graphaligner_amd/csrc/ga_ops.h run
 launch by launch): every read's runs against ops_model.rle(oracle trace types).  Cases: ops_cases.py; the same cases on the GPU are in
 test_ops_gpu.py.  On a library without the flag every test here fails: a result has no `ops`."""
 import ctypes as C
@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from graphaligner_amd import binding
+from graphaligner_amd import binding, synth
 import alphabet_cases as ac
 import ops_cases as oc
 import ops_model as om
@@ -15,7 +15,7 @@ import parity_common as pc
 
 @pytest.fixture(scope="module")
 def lib():
-    return oc.ops_lib_path()
+    return pc.emul_lib_path()
 
 
 @pytest.fixture(autouse=True, params=["lanes-first", "wave-per-read-first"])
@@ -92,12 +92,19 @@ def test_flag_changes_nothing_else(lib):
 
 def test_older_back_ends_refuse_the_flag():
     """a back end that does not code operations: the prepare is refused with GA_E_INVALID, and works without the flag"""
-    lib_path = pc.emul_lib_path()
     g, reads, seeds = oc.round_edge_batch(64)
-    gg = binding.Graph(g.nodes, g.edges, lib_path=lib_path)
+    with pc.emul_profile("emul"):
+        gg = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     with pytest.raises(RuntimeError, match=r"\(100\)"):
         gg.prepare(reads, seeds, 35, 0, binding.GA_F_OPS)
     assert len(gg.align(reads, seeds, 35)) == len(reads)
+
+
+def test_seeded_batch_equals_two_calls(lib):
+    """the twin of test_ops_gpu.py's: the driver's graph and reads (test_seed_plan.py::test_driver_output_is_byte_identical)"""
+    g = synth.bubble_graph(30000, node_len=32, seed=21)
+    reads, _ = synth.simulate_reads(g, 6, 1200, seed=77, mid_seed=True)
+    oc.case_seeded_batch_equals_two_calls(g, reads, 5, lib)
 
 
 def test_ops_string():

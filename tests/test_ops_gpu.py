@@ -3,11 +3,9 @@ ops_model.rle(oracle trace types).  Cases: ops_cases.py; the host build of the s
 without the flag every test here fails: a result has no `ops`."""
 import pytest
 
-from graphaligner_amd import binding, synth
+from graphaligner_amd import synth
 import alphabet_cases as ac
 import ops_cases as oc
-import ops_model as om
-import parity_common as pc
 
 pytestmark = pytest.mark.gpu
 
@@ -92,13 +90,4 @@ def test_seeded_batch_equals_two_calls():
     """align_reads(..., flags=GA_F_OPS) equals prepare(reads, find_seeds(reads)) with the flag, run for run, and both the oracle"""
     g = synth.bubble_graph(60000, node_len=64, seed=71)
     reads, _ = synth.simulate_reads(g, 24, 1500, seed=17, mid_seed=True)
-    gg = binding.Graph(g.nodes, g.edges)
-    gg.build_seed_index()
-    one = gg.align_reads(reads, flags=binding.GA_F_OPS)
-    found = gg.find_seeds(reads)
-    two = gg.align(reads, found.seeds, 35, 0, binding.GA_F_OPS)
-    oras = pc.oracle_results(g.nodes, g.edges, reads, [list(s) for s in found.seeds], 35)
-    aligned = oc.compare_ops(one, oras, "seeded batch")
-    assert aligned >= 12, aligned
-    for a, b in zip(one, two):
-        assert om.as_pairs(a["ops"]) == om.as_pairs(b["ops"]) and a["op_counts"] == b["op_counts"]
+    oc.case_seeded_batch_equals_two_calls(g, reads, 12)

@@ -2,8 +2,7 @@
 node's lin and the statistics on chains, cycles, self-loops, in-list orders, an inversion, a node of length 0, a node of in-degree 5
 and the larger synthetic graphs in path order and shuffled; the edge rule, independence of the node order and determinism; seeds
 under the new coordinate against the seed models; what the feature is for (support on a shuffled graph); the interface; the driver's
---seed-coord.  CPU: the seeding program built for the host (tests/emul_seed_coord); alignment through the host emulation of
-tests/emul."""
+--seed-coord.  CPU: the seeding program and the alignment programs built for the host (tests/emul)."""
 import io
 import os
 import sys
@@ -18,7 +17,6 @@ import seed_coord_common as scc
 import seed_coord_model as scm
 import seed_loci_common as slc
 import seed_model
-import seed_walk_common as swc
 import seed_walk_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lib():
-    return scc.seed_coord_emul_lib_path()
+    return pc.emul_lib_path()
 
 
 def run_case(lib, nodes, edges, **index):
@@ -294,12 +292,13 @@ def test_invalid_calls_and_rebuild(lib):
 
 
 def test_the_older_host_builds_refuse_topology():
-    """tests/emul_seed, tests/emul_seed_walks and tests/emul_seed_loci compile against the changed headers and have no topology pass:
+    """back ends without the topology pass (the profiles emul_seed, emul_seed_walks and emul_seed_loci of parity_common.PROFILES):
     GA_E_INVALID through the back end's default; file order is what they have, and asking for it is accepted"""
     g = synth.bubble_graph(6000, node_len=32, seed=3)
     reads = synth.simulate_reads(g, 2, 1000, seed=5)[0]
-    for lib_path in (sc.seed_emul_lib_path(), swc.seed_walks_emul_lib_path(), slc.seed_loci_emul_lib_path()):
-        G = binding.Graph(g.nodes, g.edges, lib_path=lib_path)
+    for profile in ("emul_seed", "emul_seed_walks", "emul_seed_loci"):
+        with pc.emul_profile(profile):
+            G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
         assert G.L.ga_graph_set_seed_coordinate(G.h, 0) == 100                 # no index yet
         G.build_seed_index()
         before = G.find_seeds(reads)
@@ -330,7 +329,7 @@ def test_seeds_under_topology_are_usable(lib):
 
 
 # ---- driver -------------------------------------------------------------------------------------------------------------------------------
-def test_driver_seed_coord(tmp_path, lib):
+def test_driver_seed_coord(tmp_path, lib, monkeypatch):
     """--find-seeds --seed-coord topology on a GFA file whose S lines are shuffled: the GAM's alignments pass the 0.7 rule against
     the truth; --seed-coord without --find-seeds and an unknown kind are refused"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -358,7 +357,8 @@ def test_driver_seed_coord(tmp_path, lib):
     assert p.findSeeds and p.seedCoord == "topology"
     p.outputDir = str(tmp_path)
     out, err = io.StringIO(), io.StringIO()
-    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err, seed_lib_path=lib)
+    monkeypatch.setenv("GA_EMUL_WITHOUT", "seeded")            # the two-call path: prepare_seeded is refused, find_seeds and prepare follow
+    written = aligner.align_reads(p, lib_path=lib, out=out, err=err)
     assert "seed coordinate: topology, 2 trees, 0 cycles cut" in out.getvalue(), out.getvalue()
     assert "seeds found for 6 of 6 reads" in out.getvalue(), out.getvalue()
     got = _decode_gam(str(tmp_path / "out.gam"))

@@ -1,11 +1,12 @@
 """The k-mer index of the graph (ga_graph_build_seed_index / ga_graph_seed_index_copy) against the model of tests/seed_model.py,
-entry for entry.  CPU: the seeding program of graphaligner_amd/csrc/ga_seed.h built for the host (tests/emul_seed); tests/test_seed_gpu.py
+entry for entry.  CPU: the seeding program of graphaligner_amd/csrc/ga_seed.h built for the host (tests/emul); tests/test_seed_gpu.py
 repeats the comparison through the product library."""
 import ctypes as C
 
 import pytest
 
 from graphaligner_amd import binding, synth
+import parity_common as pc
 import seed_common as sc
 
 GRAPHS = {
@@ -28,7 +29,7 @@ def index_cases():
 @pytest.mark.parametrize("name,k,s", list(index_cases()))
 def test_index_equals_the_model(name, k, s):
     g = GRAPHS[name]()
-    _, st = sc.check_index(g.nodes, g.edges, k, s, sc.seed_emul_lib_path())
+    _, st = sc.check_index(g.nodes, g.edges, k, s, pc.emul_lib_path())
     if name == "short8":
         # most nodes are shorter than k: few entries, no crash
         assert st["kmers_seen"] < 0.2 * 2 * sum(len(seq) for _, seq in g.nodes)
@@ -37,12 +38,12 @@ def test_index_equals_the_model(name, k, s):
 @pytest.mark.parametrize("k,s", [(k, s) for k in (11, 15, 31) for s in (0, 2, 5)])
 def test_index_of_one_long_node(k, s):
     nodes, edges = sc.big_node_graph(100000)
-    _, st = sc.check_index(nodes, edges, k, s, sc.seed_emul_lib_path())
+    _, st = sc.check_index(nodes, edges, k, s, pc.emul_lib_path())
     assert st["kmers_seen"] == 2 * (100000 - k + 1)
 
 
 def test_rebuild_replaces_the_index_and_bad_arguments_are_refused():
-    lib = sc.seed_emul_lib_path()
+    lib = pc.emul_lib_path()
     L = binding.load(lib)
     g = synth.linear_graph(5000)
     G = binding.Graph(g.nodes, g.edges, lib_path=lib)

@@ -1,8 +1,7 @@
 """ga_find_seeds_loci (one seed per locus) against the model of tests/seed_loci_model.py: seeds, support, the three locus fields,
 n_loci, hit count and truncation for every read; the hand-made cases of the rule (zigzag, gap, repeat); determinism; that the call
 leaves ga_find_seeds alone; what the feature is for (a long read gets one seed where it got two); the usability of the seeds and the
-driver's --seed-loci.  CPU: the seeding program built for the host (tests/emul_seed_loci); alignment through the host emulation of
-tests/emul."""
+driver's --seed-loci.  CPU: the seeding program and the alignment programs built for the host (tests/emul)."""
 import ctypes as C
 import io
 import os
@@ -15,7 +14,6 @@ import parity_common as pc
 import seed_common as sc
 import seed_loci_common as slc
 import seed_model
-import seed_walk_common as swc
 import seed_walk_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def world():
-    lib = slc.seed_loci_emul_lib_path()
+    lib = pc.emul_lib_path()
     g = synth.bubble_graph(30000, node_len=32, seed=3)
     G = binding.Graph(g.nodes, g.edges, lib_path=lib)
     G.build_seed_index()
@@ -48,7 +46,7 @@ def test_loci_equal_the_model(world, params):
 
 
 def test_loci_on_the_walk_index():
-    lib = slc.seed_loci_emul_lib_path()
+    lib = pc.emul_lib_path()
     g = synth.bubble_graph(30000, node_len=8, seed=3)
     G = binding.Graph(g.nodes, g.edges, lib_path=lib)
     G.build_seed_index(max_walks=64)
@@ -64,7 +62,7 @@ def test_loci_on_the_walk_index():
 
 def test_zigzag_is_one_locus():
     nodes, reads, params, inside = slc.zigzag_case()
-    G = binding.Graph(nodes, [], lib_path=slc.seed_loci_emul_lib_path())
+    G = binding.Graph(nodes, [], lib_path=pc.emul_lib_path())
     G.build_seed_index(k=params["k"], sample_shift=params["sample_shift"])
     res = slc.check_reads(G, seed_model.Model(nodes, params["k"], params["sample_shift"]), reads, **params)
     slc.check_zigzag(res, reads, inside)
@@ -72,14 +70,14 @@ def test_zigzag_is_one_locus():
 
 def test_gap_is_two_loci_and_one_seed():
     g, reads = slc.gap_case()
-    G = binding.Graph(g.nodes, g.edges, lib_path=slc.seed_loci_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     slc.check_gap(slc.check_reads(G, seed_model.Model(g.nodes), reads))
 
 
 def test_repeat_gives_one_seed_per_copy():
     g, reads = slc.repeat_case()
-    G = binding.Graph(g.nodes, g.edges, lib_path=slc.seed_loci_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     slc.check_repeat(slc.check_reads(G, seed_model.Model(g.nodes), reads, max_seeds=2))
 
@@ -97,7 +95,7 @@ def test_determinism(world):
 def test_find_seeds_is_left_alone(world):
     g, G, model = world
     reads = sc.spiked_reads(g, seed=31)
-    fresh = binding.Graph(g.nodes, g.edges, lib_path=slc.seed_loci_emul_lib_path())
+    fresh = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     fresh.build_seed_index()
     before = fresh.find_seeds(reads)
     fresh.find_seeds(reads, loci=True)
@@ -118,12 +116,13 @@ def test_find_seeds_is_left_alone(world):
 
 
 def test_the_older_host_builds_refuse():
-    """tests/emul_seed and tests/emul_seed_walks compile against the changed headers and have no findLoci: GA_E_INVALID through the
+    """back ends without findLoci (the profiles emul_seed and emul_seed_walks of parity_common.PROFILES): GA_E_INVALID through the
     back end's default, and their own call works as before"""
     g = synth.bubble_graph(6000, node_len=32, seed=3)
     reads = synth.simulate_reads(g, 2, 1000, seed=5)[0]
-    for lib in (sc.seed_emul_lib_path(), swc.seed_walks_emul_lib_path()):
-        G = binding.Graph(g.nodes, g.edges, lib_path=lib)
+    for profile in ("emul_seed", "emul_seed_walks"):
+        with pc.emul_profile(profile):
+            G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
         G.build_seed_index()
         with pytest.raises(RuntimeError, match=r"ga_find_seeds_loci failed: .*\(100\)"):
             G.find_seeds(reads, loci=True)
@@ -138,7 +137,7 @@ def test_a_long_read_gets_one_seed():
     that had a seed still has one, and the first seed is the ungrouped first seed."""
     g = synth.bubble_graph(60000, node_len=32, seed=3)
     reads = synth.simulate_reads(g, 40, 5000, seed=5)[0]
-    G = binding.Graph(g.nodes, g.edges, lib_path=slc.seed_loci_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     old = G.find_seeds(reads)
     new = slc.check_reads(G, seed_model.Model(g.nodes), reads)
@@ -158,7 +157,7 @@ def test_grouped_seeds_are_usable():
     g = synth.bubble_graph(40000, node_len=32, seed=11)
     truth = []
     reads, seeds = synth.simulate_reads(g, 100, 3000, seed=5, truth=truth)
-    row = slc.accuracy(g, reads, seeds, truth, pc.emul_lib_path(), slc.seed_loci_emul_lib_path())
+    row = slc.accuracy(g, reads, seeds, truth, pc.emul_lib_path(), pc.emul_lib_path())
     row.pop("seed_kernel_ms")
     row.pop("seed_kernel_ms_ungrouped")
     print("grouped seed accuracy (host emulation):", row)
@@ -168,7 +167,7 @@ def test_grouped_seeds_are_usable():
     assert row["seeds"] <= row["seeds_ungrouped"], row
 
 
-def test_driver_seed_loci(tmp_path):
+def test_driver_seed_loci(tmp_path, monkeypatch):
     """--find-seeds --seed-loci on files of the kind test_find_seeds.py::test_driver_finds_its_own_seeds writes: the GAM's alignments
     pass the 0.7 rule against the truth; --seed-loci without --find-seeds is refused"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -192,7 +191,8 @@ def test_driver_seed_loci(tmp_path):
     assert p.findSeeds and p.seedLoci
     p.outputDir = str(tmp_path)
     out, err = io.StringIO(), io.StringIO()
-    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err, seed_lib_path=slc.seed_loci_emul_lib_path())
+    monkeypatch.setenv("GA_EMUL_WITHOUT", "seeded")            # the two-call path: prepare_seeded is refused, find_seeds and prepare follow
+    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err)
     for n in ("short", "orphan"):
         assert "read %s has no seed hits" % n in out.getvalue() and "read %s has no seed hits" % n in err.getvalue()
     assert "one seed per locus: 6 seeds from 6 loci" in out.getvalue(), out.getvalue()

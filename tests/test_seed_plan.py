@@ -1,4 +1,4 @@
-"""Seeded batches (ga_batch_prepare_seeded) on the host build of tests/emul_seed_plan: the plan against the two-call path
+"""Seeded batches (ga_batch_prepare_seeded) on the host build of tests/emul: the plan against the two-call path
 (ga_find_seeds / ga_find_seeds_loci, then ga_batch_prepare) and against the model of tests/seed_plan_model.py, field by field; every
 clause of the rule on hand-made inputs; the results against the two-call path's; the interface's refusals; the driver."""
 import ctypes as C
@@ -12,7 +12,6 @@ import pytest
 from graphaligner_amd import aligner, binding, synth
 import parity_common as pc
 import seed_common as sc
-import seed_coord_common as scc
 import seed_loci_common as slc
 import seed_plan_common as spc
 import seed_plan_model as spm
@@ -24,7 +23,7 @@ MODE_IDS = ["hits-1", "hits-2", "hits-4", "loci"]
 @pytest.fixture(scope="module")
 def world():
     g = synth.bubble_graph(40000, node_len=32, seed=11)
-    G = binding.Graph(g.nodes, g.edges, lib_path=spc.seed_plan_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     return g, G, spm.bigraph_nodes(g.nodes)
 
@@ -50,7 +49,7 @@ def test_plan_read_counts(world, n):
 
 def test_plan_shortest_reads_on_the_walk_index():
     g = synth.bubble_graph(30000, node_len=8, seed=3)
-    G = binding.Graph(g.nodes, g.edges, lib_path=spc.seed_plan_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index(max_walks=64)
     clean = synth.simulate_reads(g, 1, 2000, sub=0.0, ins=0.0, dele=0.0, seed=8)[0][0]
     for mode in (dict(loci=False), dict(loci=True)):
@@ -73,7 +72,7 @@ def clean_world(world):
 @pytest.fixture(scope="module")
 def overlap16_world():
     nodes, edges, a = spc.overlap_graph(16)
-    G = binding.Graph(nodes, edges, overlap=16, lib_path=spc.seed_plan_emul_lib_path())
+    G = binding.Graph(nodes, edges, overlap=16, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     return G, spm.bigraph_nodes(nodes), [a[300:1900], a[2300:3700]]
 
@@ -92,7 +91,7 @@ def test_character_without_complement(clean_world, overlap16_world, case):
 
 def test_one_strand_node_and_unequal_strands():
     dnodes, (a, b, c) = spc.strand_graph()
-    G = spc.DigraphGraph(dnodes, lib_path=spc.seed_plan_emul_lib_path())
+    G = spc.DigraphGraph(dnodes, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     reads = [a[200:1700], b[200:1700], c[200:1700], a[100:1900]]
     model_nodes = [(did, len(seq)) for did, seq in dnodes]
@@ -108,7 +107,7 @@ def test_one_strand_node_and_unequal_strands():
 def test_overlap_graph():
     """a graph finalised with dbg_overlap = 4: the backward job has p + 4 rows, of which p count; the forward job's last 4 do not"""
     nodes, edges, a = spc.overlap_graph(4)
-    G = binding.Graph(nodes, edges, overlap=4, lib_path=spc.seed_plan_emul_lib_path())
+    G = binding.Graph(nodes, edges, overlap=4, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     reads = [a[300:1900], a[2300:3700]]
     plan, found = spc.check_plan(G, spm.bigraph_nodes(nodes), 4, reads, max_seeds=1)
@@ -123,7 +122,7 @@ def test_overlap_graph():
 
 def test_two_seeds_second_covered_by_the_first():
     g, reads = slc.repeat_case()
-    G = binding.Graph(g.nodes, g.edges, lib_path=spc.seed_plan_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     reads = [reads[0][:2600]]
     plan, found = spc.check_plan(G, spm.bigraph_nodes(g.nodes), 0, reads, max_seeds=2)
@@ -134,7 +133,7 @@ def test_two_seeds_second_covered_by_the_first():
 
 def test_scan_sums_stay_64_bit():
     """the layout step (slot sizes, the two scans, the writes) over fabricated job sizes whose sum passes 2^32 rows"""
-    L = C.CDLL(spc.seed_plan_emul_lib_path())
+    L = C.CDLL(pc.emul_lib_path())
     n_bw = np.array([0xffffff00, 0, 1, 0, 0xfffffe41, 65, 0], dtype=np.uint32)
     n_fw = np.array([0xfffffe00, 70, 0, 0, 64, 0xffffffc0, 5], dtype=np.uint32)
     n = len(n_bw)
@@ -179,7 +178,7 @@ def test_results_with_trace_items(world):
 def test_refusals(world):
     g, G, dnodes = world
     reads = synth.simulate_reads(g, 2, 1000, seed=5)[0]
-    lib = spc.seed_plan_emul_lib_path()
+    lib = pc.emul_lib_path()
     bare = binding.Graph(g.nodes[:200], [], lib_path=lib)
     rs = binding.ReadSet(reads, [[]] * 2)
     h = C.c_void_p()
@@ -202,20 +201,40 @@ def test_refusals(world):
 def test_older_host_builds_refuse(world):
     g, G, dnodes = world
     reads = synth.simulate_reads(g, 2, 1000, seed=5)[0]
-    for lib in (sc.seed_emul_lib_path(), slc.seed_loci_emul_lib_path(), scc.seed_coord_emul_lib_path()):
-        old = binding.Graph(g.nodes, g.edges, lib_path=lib)
+    for profile in ("emul_seed", "emul_seed_loci", "emul_seed_coord"):
+        with pc.emul_profile(profile):
+            old = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
         old.build_seed_index()
         with pytest.raises(binding.SeededUnsupported):
             old.prepare_seeded(reads)
         assert old.find_seeds(reads).seeds == G.find_seeds(reads).seeds
+    with pc.emul_profile("emul"):
+        unseeded = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     with pytest.raises(binding.SeededUnsupported):
-        binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path()).prepare_seeded(reads)
+        unseeded.prepare_seeded(reads)
+
+
+def test_the_switch_is_read_per_graph():
+    """GA_EMUL_WITHOUT belongs to the graph uploaded under it, not to the process or the library"""
+    g = synth.bubble_graph(6000, node_len=32, seed=3)
+    reads = synth.simulate_reads(g, 2, 300, seed=5)[0]
+    lib = pc.emul_lib_path()
+    with pc.emul_profile("emul_seed_coord"):
+        without = binding.Graph(g.nodes, g.edges, lib_path=lib)
+    with_it = binding.Graph(g.nodes, g.edges, lib_path=lib)
+    for graph in (without, with_it):
+        graph.build_seed_index()
+    with pytest.raises(binding.SeededUnsupported):
+        without.prepare_seeded(reads)
+    with_it.prepare_seeded(reads).close()
+    with pytest.raises(binding.SeededUnsupported):
+        without.prepare_seeded(reads)
 
 
 def test_find_seeds_is_left_alone(world):
     g, G, dnodes = world
     reads = sc.spiked_reads(g, seed=31)
-    fresh = binding.Graph(g.nodes, g.edges, lib_path=spc.seed_plan_emul_lib_path())
+    fresh = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     fresh.build_seed_index()
     before = spc.plain_seeds(fresh.find_seeds(reads)), spc.plain_seeds(fresh.find_seeds(reads, loci=True))
     fresh.prepare_seeded(reads).close()
@@ -224,8 +243,8 @@ def test_find_seeds_is_left_alone(world):
 
 
 @pytest.mark.parametrize("loci", [False, True], ids=["hits", "loci"])
-def test_driver_output_is_byte_identical(tmp_path, loci):
-    """--find-seeds through seeded batches (one library that seeds and aligns) against the two-call path (the two older libraries)"""
+def test_driver_output_is_byte_identical(tmp_path, loci, monkeypatch):
+    """--find-seeds through seeded batches against the two-call path (the same back end with seeded batches withheld)"""
     g = synth.bubble_graph(30000, node_len=32, seed=21)
     reads, _ = synth.simulate_reads(g, 6, 1200, seed=77, mid_seed=True)
     names = ["r%d/x:%d" % (i, i) for i in range(len(reads))] + ["short", "orphan"]
@@ -233,12 +252,13 @@ def test_driver_output_is_byte_identical(tmp_path, loci):
     (tmp_path / "g.gfa").write_text(g.gfa())
     (tmp_path / "r.fq").write_text("".join("@%s\n%s\n+\n%s\n" % (n, r, "I" * len(r)) for n, r in zip(names, reads)))
     outs = []
-    for tag, kw in (("seeded", dict(lib_path=spc.seed_plan_emul_lib_path())), ("two", dict(lib_path=pc.emul_lib_path(), seed_lib_path=scc.seed_coord_emul_lib_path()))):
+    for tag, without in (("seeded", ""), ("two", "seeded")):
         argv = ["-g", str(tmp_path / "g.gfa"), "-f", str(tmp_path / "r.fq"), "--find-seeds", "-a", str(tmp_path / (tag + ".gam")), "-t", "1", "-b", "35"]
         params = aligner.parse_args(argv + (["--seed-loci"] if loci else []))
         params.outputDir = str(tmp_path)                                   # (the per-read files: the same names both times)
         out, err = io.StringIO(), io.StringIO()
-        written = aligner.align_reads(params, out=out, err=err, **kw)
+        monkeypatch.setenv("GA_EMUL_WITHOUT", without)
+        written = aligner.align_reads(params, lib_path=pc.emul_lib_path(), out=out, err=err)
         # (a GAM file is gzip members, whose headers carry the time of writing: the bytes compared are the members' contents)
         plain = lambda f: gzip.decompress((tmp_path / f).read_bytes()) if f.endswith(".gam") else (tmp_path / f).read_bytes()
         per_read = [(f, plain(f)) for f in sorted(os.listdir(tmp_path)) if f.startswith(("alignment_0_", "trace_0_"))]

@@ -1,4 +1,4 @@
-"""The pipelines with seeds=None over two ranks (gloo, host build of tests/emul_seed_plan): align_sharded and align_queued with
+"""The pipelines with seeds=None over two ranks (gloo, host build of tests/emul): align_sharded and align_queued with
 find_seeds=... gathered on rank 0 equal the same functions with the seeds passed in, for the three result forms."""
 import os
 import socket
@@ -59,8 +59,8 @@ def _worker(rank, world, port, lib, q):
 def test_two_ranks_without_seeds_equal_two_ranks_with_seeds():
     import torch.multiprocessing as mp
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import seed_plan_common as spc
-    lib = spc.seed_plan_emul_lib_path()
+    import parity_common as pc
+    lib = pc.emul_lib_path()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()

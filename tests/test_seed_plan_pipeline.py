@@ -1,9 +1,10 @@
 """The pipelines with seeds=None: sharding.run_overlapped, align_queued and align_sharded with find_seeds=dict(params=..., loci=...) make
 seeded batches (Graph.prepare_seeded) and must give what the same functions give with the seeds of Graph.find_seeds passed in, for all
-three result forms.  Host build of tests/emul_seed_plan."""
+three result forms.  Host build of tests/emul."""
 import pytest
 
 from graphaligner_amd import binding, sharding, synth
+import parity_common as pc
 import seed_plan_common as spc
 
 SUMMARY_FIELDS = ("status", "failed", "score", "n_mappings", "alignment_start", "alignment_end", "query_position", "column_updates")
@@ -12,7 +13,7 @@ SUMMARY_FIELDS = ("status", "failed", "score", "n_mappings", "alignment_start", 
 @pytest.fixture(scope="module")
 def world():
     g = synth.bubble_graph(40000, node_len=32, seed=11)
-    G = binding.Graph(g.nodes, g.edges, lib_path=spc.seed_plan_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index()
     reads = spc.mixed_reads(g, 26, length=700, seed=9)
     reads = [r[: 400 + (53 * i) % 300] if len(r) > 300 else r for i, r in enumerate(reads)]      # ragged lengths

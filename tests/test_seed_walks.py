@@ -1,8 +1,8 @@
 """The walk index (ga_graph_build_seed_index_walks / ga_graph_seed_index_walk_stats: k-mers of walks that leave a node through its
 out-edges, for graphs of nodes shorter than k) against the model of tests/seed_walk_model.py, entry for entry and seed for seed; the
 rule's corner cases on hand-made graphs; the usability of the seeds on a graph of 8-bp nodes; the driver's --seed-walks.
-CPU: the seeding program of graphaligner_amd/csrc/ga_seed.h built for the host (tests/emul_seed_walks), alignment through the host
-emulation of tests/emul; tests/test_seed_walks_gpu.py repeats the comparisons through the product library."""
+CPU: the seeding program of graphaligner_amd/csrc/ga_seed.h and the alignment programs built for the host
+(tests/emul); tests/test_seed_walks_gpu.py repeats the comparisons through the product library."""
 import ctypes as C
 import io
 import os
@@ -37,7 +37,7 @@ def entries(G):
 @pytest.mark.parametrize("name,k,s,max_walks", list(swc.walk_index_cases()))
 def test_walk_index_equals_the_model(name, k, s, max_walks):
     g = swc.GRAPHS[name]()
-    _, _, st, ws = swc.check_walk_index(g.nodes, g.edges, k, s, max_walks, swc.seed_walks_emul_lib_path())
+    _, _, st, ws = swc.check_walk_index(g.nodes, g.edges, k, s, max_walks, pc.emul_lib_path())
     if name == "short8":
         # the in-node index of this graph is (nearly) empty (test_seed_index.py); here nearly every base starts a k-mer
         assert ws["tail_starts_skipped"] == 0 and st["kmers_seen"] > 0.9 * 2 * sum(len(seq) for _, seq in g.nodes)
@@ -52,7 +52,7 @@ def test_two_branches_of_equal_text_give_one_entry():
     a, b = text(20, 1), text(20, 2)
     nodes = [(1, a), (2, "ACGT"), (3, "ACGT"), (4, b)]
     edges = [(1, False, 2, False), (1, False, 3, False), (2, False, 4, False), (3, False, 4, False)]
-    G, model, st, ws = swc.check_walk_index(nodes, edges, 11, 0, 64, swc.seed_walks_emul_lib_path())
+    G, model, st, ws = swc.check_walk_index(nodes, edges, 11, 0, 64, pc.emul_lib_path())
     # the tail starts of node 1 (index 1), offsets 10..19, have two walks each with the same text
     assert ws["duplicates_dropped"] >= 10 and ws["tail_starts_skipped"] == 0
     mine = [e for e in entries(G) if e[1] == 1 and e[2] >= 10]
@@ -60,14 +60,14 @@ def test_two_branches_of_equal_text_give_one_entry():
     for key, _, o in mine:
         assert key == seed_walk_model.key_of((a[o:] + "ACGT" + b)[:11])
     # with max_walks 1 those starts have one walk too many
-    _, _, _, ws1 = swc.check_walk_index(nodes, edges, 11, 0, 1, swc.seed_walks_emul_lib_path())
+    _, _, _, ws1 = swc.check_walk_index(nodes, edges, 11, 0, 1, pc.emul_lib_path())
     assert ws1["tail_starts_skipped"] >= 10
 
 
 def test_a_dead_end_inside_k_bases_gives_nothing():
     a = text(20, 3)
     nodes = [(1, a), (2, "ACG")]
-    G, model, st, ws = swc.check_walk_index(nodes, [(1, False, 2, False)], 11, 0, 64, swc.seed_walks_emul_lib_path())
+    G, model, st, ws = swc.check_walk_index(nodes, [(1, False, 2, False)], 11, 0, 64, pc.emul_lib_path())
     # forward node 1: offsets 0..9 lie inside it; 10, 11, 12 reach 11 bases with the 3 of node 2; later ones end before
     assert sorted(e[2] for e in entries(G) if e[1] == 1) == list(range(13))
     assert ws["tail_starts"] == 2 * (10 + 3) and ws["walk_kmers"] == 3 + 3          # reverse strand: node 2' (3 bp) walks into node 1'
@@ -77,7 +77,7 @@ def test_a_dead_end_inside_k_bases_gives_nothing():
 def test_an_edge_with_a_reverse_flag():
     a, b = text(20, 4), text(20, 5)
     nodes = [(1, a), (2, b)]
-    G, model, st, ws = swc.check_walk_index(nodes, [(1, False, 2, True)], 11, 0, 64, swc.seed_walks_emul_lib_path())
+    G, model, st, ws = swc.check_walk_index(nodes, [(1, False, 2, True)], 11, 0, 64, pc.emul_lib_path())
     # node 1 forward (index 1) goes on into node 2 reversed; node 2 forward (index 3) into node 1 reversed
     got = {(n, o): key for key, n, o in entries(G)}
     for o in range(10, 20):
@@ -91,7 +91,7 @@ def test_a_self_loop_on_a_three_bp_node():
     a, b = text(20, 6), text(20, 7)
     nodes = [(1, a), (2, "ACG"), (3, b)]
     edges = [(1, False, 2, False), (2, False, 2, False), (2, False, 3, False)]
-    G, model, st, ws = swc.check_walk_index(nodes, edges, 11, 0, 64, swc.seed_walks_emul_lib_path())
+    G, model, st, ws = swc.check_walk_index(nodes, edges, 11, 0, 64, pc.emul_lib_path())
     keys_of_loop_node = set(key for key, n, o in entries(G) if n == 3 and o == 0)
     # from the loop node's first base: around the loop 0, 1, 2 times and out, or three more times around
     want = set(seed_walk_model.key_of(("ACG" * r + b)[:11]) for r in (1, 2, 3)) | {seed_walk_model.key_of(("ACG" * 4)[:11])}
@@ -106,7 +106,7 @@ def fan(order):
 
 def test_a_fan_over_the_cap_is_skipped_and_counted():
     nodes, edges = fan(range(5))
-    lib = swc.seed_walks_emul_lib_path()
+    lib = pc.emul_lib_path()
     G, _, _, ws = swc.check_walk_index(nodes, edges, 11, 0, 4, lib)
     assert ws["tail_starts_skipped"] == 10                                          # node 1's ten tail starts have five walks each
     assert [e for e in entries(G) if e[1] == 1 and e[2] >= 10] == []
@@ -118,7 +118,7 @@ def test_a_fan_over_the_cap_is_skipped_and_counted():
 
 @pytest.mark.parametrize("max_walks", [4, 64])
 def test_the_order_of_the_neighbours_does_not_matter(max_walks):
-    lib = swc.seed_walks_emul_lib_path()
+    lib = pc.emul_lib_path()
     got = []
     for order in ((0, 1, 2, 3, 4), (3, 0, 4, 2, 1)):
         nodes, edges = fan(order)
@@ -136,7 +136,7 @@ def test_the_order_of_the_neighbours_does_not_matter(max_walks):
 @pytest.mark.parametrize("k,n_entries", [(15, 6885), (31, 7822)])
 def test_the_index_does_not_depend_on_where_the_nodes_are_cut(k, n_entries):
     """the same sequence and variants cut into 8-bp and into 32-bp nodes: the same keys, as long as no tail start is skipped"""
-    lib = swc.seed_walks_emul_lib_path()
+    lib = pc.emul_lib_path()
     keys = []
     for node_len in (8, 32):
         g = synth.bubble_graph(12000, node_len=node_len, seed=3)
@@ -150,7 +150,7 @@ def test_the_index_does_not_depend_on_where_the_nodes_are_cut(k, n_entries):
 
 def test_the_cap_is_exercised():
     g = synth.cyclic_graph(3000, node_len=16)
-    lib = swc.seed_walks_emul_lib_path()
+    lib = pc.emul_lib_path()
     _, _, _, ws = swc.check_walk_index(g.nodes, g.edges, 31, 0, 4, lib)
     assert ws["tail_starts_skipped"] > 0
     _, _, _, ws = swc.check_walk_index(g.nodes, g.edges, 31, 0, 64, lib)
@@ -160,7 +160,7 @@ def test_the_cap_is_exercised():
 @pytest.mark.parametrize("name", ["bubbles32", "linear", "cyclic16"])
 def test_the_in_node_entries_are_those_of_the_old_index(name):
     g = swc.GRAPHS[name]()
-    G = binding.Graph(g.nodes, g.edges, lib_path=swc.seed_walks_emul_lib_path())
+    G = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
     G.build_seed_index(k=15, sample_shift=2)
     old = entries(G)
     G.build_seed_index(k=15, sample_shift=2, max_walks=64)
@@ -170,7 +170,7 @@ def test_the_in_node_entries_are_those_of_the_old_index(name):
 
 
 def test_bad_arguments_are_refused_and_a_rebuild_replaces_the_index():
-    lib = swc.seed_walks_emul_lib_path()
+    lib = pc.emul_lib_path()
     L = binding.load(lib)
     g = synth.bubble_graph(6000, node_len=8, seed=3)
     G = binding.Graph(g.nodes, g.edges, lib_path=lib)
@@ -200,15 +200,15 @@ def test_bad_arguments_are_refused_and_a_rebuild_replaces_the_index():
     assert L.ga_graph_finalize(h, 0) == 0
     assert L.ga_graph_build_seed_index_walks(h, 15, 2, 64) == 101                   # GA_E_NO_DEVICE: not uploaded
     L.ga_graph_destroy(h)
-    # the library that only knows the in-node build refuses through the back end's default
-    old = binding.load(sc.seed_emul_lib_path())
-    O = binding.Graph(g.nodes, g.edges, lib_path=sc.seed_emul_lib_path())
-    assert old.ga_graph_build_seed_index_walks(O.h, 15, 2, 64) == 100
+    # a back end that only knows the in-node build refuses through the back end's default
+    with pc.emul_profile("emul_seed"):
+        O = binding.Graph(g.nodes, g.edges, lib_path=pc.emul_lib_path())
+    assert O.L.ga_graph_build_seed_index_walks(O.h, 15, 2, 64) == 100
 
 
 # ---- seeds ------------------------------------------------------------------------------------------------------------------------
 def test_walk_seeds_equal_the_model():
-    lib = swc.seed_walks_emul_lib_path()
+    lib = pc.emul_lib_path()
     g = synth.bubble_graph(30000, node_len=8, seed=3)
     G = binding.Graph(g.nodes, g.edges, lib_path=lib)
     G.build_seed_index(max_walks=64)
@@ -250,7 +250,7 @@ def test_walk_seeds_are_usable():
     g = synth.bubble_graph(40000, node_len=8, seed=11)
     truth = []
     reads, seeds = synth.simulate_reads(g, 100, 3000, seed=5, truth=truth)
-    row = swc.accuracy_walks(g, reads, seeds, truth, pc.emul_lib_path(), swc.seed_walks_emul_lib_path(), 64)
+    row = swc.accuracy_walks(g, reads, seeds, truth, pc.emul_lib_path(), pc.emul_lib_path(), 64)
     row.pop("seed_kernel_ms")
     print("walk seed accuracy (host emulation):", row)
     sc.record("seed_walks_accuracy_cpu.json", "bubble_graph(40000, node_len=8, seed=11), 100 x 3000 bp, seed=5, max_walks=64", row)
@@ -259,7 +259,7 @@ def test_walk_seeds_are_usable():
     assert row["good_true_seeds"] >= 90, row
 
 
-def test_driver_seed_walks(tmp_path):
+def test_driver_seed_walks(tmp_path, monkeypatch):
     """--find-seeds --seed-walks 64 on a GFA of 8-bp nodes: the GAM's alignments pass the 0.7 rule against the truth; without
     --seed-walks the same command finds no seed for any read"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -283,7 +283,8 @@ def test_driver_seed_walks(tmp_path):
     p = aligner.parse_args(base + ["--find-seeds"])
     p.outputDir = str(tmp_path)
     out, err = io.StringIO(), io.StringIO()
-    aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err, seed_lib_path=swc.seed_walks_emul_lib_path())
+    monkeypatch.setenv("GA_EMUL_WITHOUT", "seeded")            # the two-call path: prepare_seeded is refused, find_seeds and prepare follow
+    aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err)
     for n in names:
         assert "read %s has no seed hits" % n in out.getvalue()
     assert "seed index: 0 entries" in out.getvalue() and "tail starts" not in out.getvalue()
@@ -292,7 +293,7 @@ def test_driver_seed_walks(tmp_path):
     assert p.findSeeds and p.seedWalks == 64
     p.outputDir = str(tmp_path)
     out, err = io.StringIO(), io.StringIO()
-    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err, seed_lib_path=swc.seed_walks_emul_lib_path())
+    written = aligner.align_reads(p, lib_path=pc.emul_lib_path(), out=out, err=err)
     assert "has no seed hits" not in out.getvalue()
     assert "walks: 0 of " in out.getvalue() and "tail starts skipped (more than 64 walks)" in out.getvalue()
     got = _decode_gam(str(tmp_path / "out.gam"))

@@ -1,4 +1,4 @@
-"""Bit-vector bands of more than 256 nodes: the ladder's pass with 4 096 band nodes, checked on the host (tests/emul_wide: the
+"""Bit-vector bands of more than 256 nodes: the ladder's pass with 4 096 band nodes, checked on the host (tests/emul: the
 device program with run_job<4096,true> behind <256,true>) against real libstdc++ containers and against the oracle.  The GPU
 tests of the same cases are in test_wide_bands_gpu.py."""
 import ctypes as C
@@ -13,7 +13,7 @@ import wide_cases as wc
 
 @pytest.fixture(scope="module")
 def lib():
-    return wc.wide_lib_path()
+    return pc.emul_lib_path()
 
 
 @pytest.fixture(scope="module")
@@ -97,9 +97,11 @@ def test_parity_with_unclean_buffers(lib, name, switch, monkeypatch):
 def test_new_ground(lib):
     """the ladder without the pass gives these reads up (GA_S_CAPACITY); with it they align"""
     nodes, edges, reads, seeds = wc.fan_batch(*[wc.CASES["300x64"][i] for i in (0, 1, 2, 3, 6)])
-    old, _ = pc.run_both(nodes, edges, reads, seeds, 35, lib_path=pc.emul_lib_path())
+    with pc.emul_profile("emul"):
+        old, _ = pc.run_both(nodes, edges, reads, seeds, 35, lib_path=lib)
     assert [d["status"] for d in old] == [10] * len(reads)
-    new, _ = pc.run_both(nodes, edges, reads, seeds, 35, lib_path=lib)
+    with pc.emul_profile("emul_wide"):
+        new, _ = pc.run_both(nodes, edges, reads, seeds, 35, lib_path=lib)
     assert [d["status"] for d in new] == [0] * len(reads)
 
 

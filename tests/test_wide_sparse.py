@@ -1,6 +1,6 @@
 """Bands of 200 000 cells and more with more than 256 nodes: the ladder's last pass, run_job<4096,true,true> (the sparse method and
-the backtrace override with 4 096 band nodes and the tables of SparseLimits<4096>), checked on the host: tests/emul_wide_sparse is
-tests/emul_wide's ladder plus that pass.  The GPU tests of the same cases are in test_wide_sparse_gpu.py.  Without the pass every
+the backtrace override with 4 096 band nodes and the tables of SparseLimits<4096>), checked on the host (tests/emul); the ladder
+without that pass is the same library with the pass withheld (parity_common.PROFILES).  The GPU tests of the same cases are in test_wide_sparse_gpu.py.  Without the pass every
 fan read here ends as GA_S_CAPACITY (status 10)."""
 import ctypes as C
 
@@ -15,7 +15,7 @@ import wide_sparse_cases as wsc
 
 @pytest.fixture(scope="module")
 def lib():
-    return wsc.lib_path()
+    return pc.emul_lib_path()
 
 
 @pytest.fixture(scope="module")
@@ -136,9 +136,11 @@ def test_new_ground(lib):
     """the ladder without the pass gives these reads up (GA_S_CAPACITY); with it they align"""
     case = wsc.CASES["300x700"][0]
     nodes, edges, reads, seeds = wsc.batch(case)
-    old, _ = pc.run_both(nodes, edges, reads, seeds, case[4], lib_path=wc.wide_lib_path())
+    with pc.emul_profile("emul_wide"):
+        old, _ = pc.run_both(nodes, edges, reads, seeds, case[4], lib_path=lib)
     assert [d["status"] for d in old] == [10] * len(reads)
-    new, _ = pc.run_both(nodes, edges, reads, seeds, case[4], lib_path=lib)
+    with pc.emul_profile("emul_wide_sparse"):
+        new, _ = pc.run_both(nodes, edges, reads, seeds, case[4], lib_path=lib)
     assert [d["status"] for d in new] == [0] * len(reads)
 
 
@@ -158,16 +160,20 @@ def _same(a, b, ctx):
 def test_ladders_agree_on_a_wide_bit_vector_case(lib, hooks):
     case = wc.CASES["300x64"]
     nodes, edges, reads, seeds = wc.fan_batch(*[case[i] for i in (0, 1, 2, 3, 6)])
-    a, _ = pc.run_both(nodes, edges, reads, seeds, case[4], ramp=case[5], lib_path=wc.wide_lib_path())
-    b, _ = pc.run_both(nodes, edges, reads, seeds, case[4], ramp=case[5], lib_path=lib)
+    with pc.emul_profile("emul_wide"):
+        a, _ = pc.run_both(nodes, edges, reads, seeds, case[4], ramp=case[5], lib_path=lib)
+    with pc.emul_profile("emul_wide_sparse"):
+        b, _ = pc.run_both(nodes, edges, reads, seeds, case[4], ramp=case[5], lib_path=lib)
     assert hooks.ga_emul_wide_sparse_jobs_taken() == 0
     _same(a, b, "300x64")
     assert [d["status"] for d in b] == [0] * len(reads)
 
 
 def test_ladders_agree_on_the_bit_vector_limit(lib):
-    a, _ = wc.check_limit(wc.wide_lib_path())
-    b, _ = wc.check_limit(lib)
+    with pc.emul_profile("emul_wide"):
+        a, _ = wc.check_limit(lib)
+    with pc.emul_profile("emul_wide_sparse"):
+        b, _ = wc.check_limit(lib)
     _same(a, b, "wide_cases.LIMIT")
 
 
@@ -175,8 +181,10 @@ def test_ladders_agree_on_the_pinned_capacity_misses(lib, hooks):
     """the 256 variant's own per-row limit: its misses are GA_CAP_HEAP, which the new pass does not take"""
     g, reads, seeds, draws, oras = rc.capacity_batch()
     bw, ramp = rc.CAPACITY_FAN[4], rc.CAPACITY_FAN[5]
-    a, _ = pc.run_both(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=wc.wide_lib_path())
-    b, _ = pc.run_both(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib)
+    with pc.emul_profile("emul_wide"):
+        a, _ = pc.run_both(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib)
+    with pc.emul_profile("emul_wide_sparse"):
+        b, _ = pc.run_both(g.nodes, g.edges, reads, seeds, bw, ramp=ramp, lib_path=lib)
     assert hooks.ga_emul_wide_sparse_jobs_taken() == 0
     _same(a, b, "capacity batch")
     assert {d for d, x in zip(draws, b) if x["status"] == 10} == set(rc.CAPACITY_MISSES)

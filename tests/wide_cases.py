@@ -1,21 +1,17 @@
 """Cases for the ladder's pass with 4 096 band nodes (bit-vector bands of more than 256 nodes), shared by tests/test_wide_bands.py
-(host emulation, tests/emul_wide) and tests/test_wide_bands_gpu.py (the product library).
+(host emulation, tests/emul) and tests/test_wide_bands_gpu.py (the product library).
 
 The graphs are fans (synth.FanGraph) of many SHORT branches: when an alignment nears the stem's end the projected band holds the
 stem, every branch and, a little later, every tail -- hundreds to thousands of nodes, but fewer than 200 000 cells, so the reference
 aligns them with its ordinary bit-vector path.  Every case is compared with the oracle, every field; the oracle must report status 0
 and no sparse slice for every read, so that a case cannot quietly turn into a sparse one."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 from graphaligner_amd import synth
 import parity_common as pc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WIDE_SO = os.path.join(ROOT, "tests", "_build", "libga_emul_wide.so")
 
 HEAD_LEN, STEM_LEN, READ_LEN = 300, 600, 1400
 
@@ -30,11 +26,6 @@ CASES = {
     "cyclic-700x16-ramp": (700, 16, 8, 60, 35, 50, True),
 }
 LIMIT = (4200, 8, 4, 8, 35, 0, False)                    # 8 402 nodes: more than the widest tables hold
-
-
-def wide_lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_wide")])
-    return WIDE_SO
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,19 +1,15 @@
 """Cases for the ladder's last pass: bands of 200 000 cells and more with more than 256 nodes -- the sparse method and the backtrace
 override with 4 096 band nodes (run_job<4096,true,true>, ga_wide_sparse_kernel).  Shared by tests/test_wide_sparse.py (host emulation,
-tests/emul_wide_sparse) and tests/test_wide_sparse_gpu.py (the product library).
+tests/emul) and tests/test_wide_sparse_gpu.py (the product library).
 
 The graphs are the fans of wide_cases.fan_batch with LONG branches or very many of them: when an alignment nears the stem's end the
 projected band holds the stem and every branch -- 300 to 4 000 nodes and more than 200 000 cells, where the reference leaves its bit
 vectors.  What the oracle does with each case is asserted here from its own results (statuses, sparse slices), so that a case
 cannot quietly stop being a wide sparse one; every read is then compared with the oracle in every field."""
-import os
-import subprocess
 
 import parity_common as pc
 import wide_cases as wc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WIDE_SPARSE_SO = os.path.join(ROOT, "tests", "_build", "libga_emul_wide_sparse.so")
 
 # name -> ((branches, branch_len, shared, tail_len, band, ramp, cyclic), the oracle's status per read, its sparse slices per read
 # (None: a read the oracle ends in an assertion))
@@ -32,11 +28,6 @@ CASES = {
 LIMIT = (4200, 50, 6, 40, 3, 0, False)
 SMALLEST = ("300x700", "700x300-ramp", "300x700-ramp")
 MIN_SPARSE_ALIGNED = 15      # reads across CASES that the oracle aligns over at least one sparse slice
-
-
-def lib_path():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul_wide_sparse")])
-    return WIDE_SPARSE_SO
 
 
 def batch(case):
