@@ -16,6 +16,7 @@
 #include "../../include/graphaligner_amd.h"
 #include "ga_backend.h"
 #include "ga_kernel.h"
+#include "ga_ladder.h"
 #include "ga_lanes.h"
 #include "ga_seed_dev.h"
 #include "ga_plan.h"
@@ -841,20 +842,16 @@ struct DevBatch : GaBackendBatch
 		return 0;
 	}
 
-	static bool isCapacity(int s) { return s == GA_CAP_NODES || s == GA_CAP_COLS || s == GA_CAP_ARENA || s == GA_CAP_TRACE || s == GA_CAP_HEAP || s == GA_PUNT || s == GA_NOT_RUN; }
-	// bands with cycles and ramp redos: only the general wave-per-read variants carry those paths
-	static bool needsGeneral(int s) { return s == GA_UNSUPPORTED_CYCLE || s == GA_UNSUPPORTED_RAMP; }
-	// what a lanes = reads variant with larger tables can still take
-	static bool widerLanes(int s) { return s == GA_CAP_NODES || s == GA_CAP_COLS || s == GA_CAP_ARENA || s == GA_CAP_TRACE || s == GA_CAP_HEAP; }
-	// what the pass with 4 096 band nodes is for: the band tables or the projection heap of 256 nodes overflowed
-	static bool widerTables(int s) { return s == GA_CAP_NODES || s == GA_CAP_HEAP; }
+	// ---- the ladder: ga_ladder.h decides which variant runs over which jobs, in which order; here is how each one is run ------------
+	// lanes = reads variants <10,64>, <24,32>, <56,16>: arena rows per lane and slice -- the band's columns rounded up to blocks of 8 per
+	// node, with room for the widest slices.  (10 / 24 / 56 band nodes per lane = 4 / 2 / 1 waves per CU next to the 12.8 KB block image.
+	// The wider tables trade lanes for LDS per lane: 32 and 16 lanes per wave keep four waves on every CU -- the same number of reads in
+	// flight as 64-lane waves that leave three SIMDs of four idle, in four times as many instruction streams.)
+	static constexpr uint32_t kLanesRowsPerSlice[] = {288, 480, 768};
 
 	// one launch of the lanes = reads kernel over `list` (job indices, longest first)
 	template <int N, int LW> int lanesPass(const std::vector<uint32_t>& list, uint32_t rowsPerSlice, bool first)
 	{
-		if (list.empty()) return 0;
-		for (uint32_t i : list) passOf[i] = (uint8_t)passNo;
-		passNo++;
 		gal::GaLanesLaunch P;
 		memset(&P, 0, sizeof(P));
 		P.graph = L.graph; P.hmm = L.hmm; P.eq = dEq; P.jobs = L.jobs; P.outs = L.outs;
@@ -935,79 +932,137 @@ struct DevBatch : GaBackendBatch
 		return rc;
 	}
 
-	// (MAXN > 256: the variants with their band tables in HBM.  ga_wide_kernel takes only the jobs whose band or projection heap
-	// overflowed; ga_wide_sparse_kernel only those that the sparse variant before it left with GA_CAP_NODES)
+	// the wave-per-read variants: the kernel behind each and what the host has to know about it.  The two with 4 096 band nodes keep
+	// their WaveState in the wave's scratch slot in HBM (stateBytes); the two that carry the sparse method have generation-stamped
+	// tables, sized for sparseNodes band nodes, that start from zero once per launch.
+	struct WaveKernel
+	{
+		void (*kernel)(GaLaunch);
+		int maxN;
+		bool general;
+		uint64_t stateBytes;
+		int sparseNodes;          // 0: the variant does not carry the sparse method
+		bool clearSlotBySlot;     // the sparse tables are some 160 MB of a 360 MB slot: cleared slot by slot, and without them cleared nothing is launched
+	};
 	// the slots of ga_wide_sparse_kernel are some 360 MB each (arena for 2^20-column slices, 2^23 queue entries): a fallback for a few
 	// jobs, capped so that a batch of many such jobs does not claim the whole device for it
 	static constexpr uint32_t kWideSparseSlots = 32;
-	template <int MAXN, bool GENERAL, bool SPARSE = false> int retryPass(uint32_t capCols, uint64_t arenaWordsPerSlice, uint32_t traceMul, uint32_t wavesPerCuRetry, bool takeCapacity, bool takeGeneral,
-	                                                                    uint64_t arenaWordsExtra = 0)
+	// the scratch slot of each wave-per-read rung, in the order of gald::kRungs
+	struct WaveGeom
 	{
-		constexpr bool kWide = gak::Limits<MAXN>::kStateInHbm;
-		static_assert(!kWide || (MAXN == kWideNodes && GENERAL), "two variants keep their state in HBM: <4096,true> and <4096,true,true>");
-		std::vector<uint32_t> again;
-		for (uint32_t i : orderHost)
-		{
-			if (kWide && SPARSE) { if (outs[i].status == GA_CAP_NODES) again.push_back(i); }
-			else if (kWide) { if (widerTables(outs[i].status)) again.push_back(i); }
-			else if ((takeCapacity && isCapacity(outs[i].status)) || (takeGeneral && needsGeneral(outs[i].status)) || (SPARSE && outs[i].status == GA_UNSUPPORTED_BAND)) again.push_back(i);
-		}
-		if (again.empty()) return 0;
+		uint32_t capCols;
+		uint64_t arenaWordsPerSlice;
+		uint32_t traceMul, wavesPerCu;
+		uint64_t arenaWordsExtra;
+		uint32_t slotCap;         // 0: as many slots as fit
+	};
+	static constexpr WaveGeom kWaveGeom[] = {
+		// <GA_FIRST_N,false>: the lean variant over everything (32 band nodes in LDS, 24 waves per CU)
+		{4096, 3 * 64 + 5 * 800, 2, 24, 0, 0},
+		// <64,false>: 64 band nodes in LDS
+		{8192, 3 * 64 + 5 * 2048, 3, 12, 0, 0},
+		// <64,true>, <256,true>: the general variants, which also carry the paths for bands with cycles and for ramp redos; 256 band
+		// nodes with large buffers
+		{8192, 3 * 64 + 5 * 4096, 4, 8, 0, 0},
+		{65536, 3 * 256 + 5 * 8192, 6, 4, 0, 0},
+		// <4096,true>: bit-vector bands of more than 256 nodes (tangles of short nodes, wide bubbles, fans): 4 096 band nodes with the
+		// tables in HBM, one wave per CU.  A bit-vector band has at most 199 999 columns.  Arena per slice: the node table of 4 096 nodes
+		// and 32 768 columns -- four times the figure of the pass before for sixteen times its nodes, because what overflows 256 band
+		// nodes is short nodes (the passes before allow 32 columns per table node; 8 per node here), and few slices of a job are that
+		// wide.  A job that needs more reports GA_CAP_ARENA and goes on to the next pass like every other capacity miss.
+		{kCutoffCols, 3 * (uint64_t)kWideNodes + 5 * 32768, 8, 1, 0, 0},
+		// <256,true,true>: bands of 200 000 cells and more (the reference's sparse method and backtrace override, ga_sparse.h), with room
+		// for every column of every node such a slice touches: 2^20 columns
+		{1u << 20, 3 * 256 + 5 * 20000, 8, 1, 48ull << 20, 0},
+		// <4096,true,true>: such bands with more than 256 nodes (fans and tangles of hundreds to thousands of nodes): the same with
+		// 4 096 band nodes, the state in HBM and tables sized for it.  Arena as above.  No such job, no launch.
+		{1u << 20, 3 * (uint64_t)kWideNodes + 5 * 20000, 8, 1, 48ull << 20, kWideSparseSlots},
+	};
+	static_assert(sizeof(kWaveGeom) / sizeof(kWaveGeom[0]) == sizeof(gald::kRungs) / sizeof(gald::kRungs[0]), "one scratch geometry per wave-per-read rung");
+
+	// one launch of a wave-per-read kernel over `again` (job indices, longest first)
+	int wavePass(const WaveKernel& k, const WaveGeom& geo, const std::vector<uint32_t>& again)
+	{
 		if (ensureRows()) return GA_E_DEVICE;
-		for (uint32_t i : again) passOf[i] = (uint8_t)passNo;
-		passNo++;
-		st.jobs_retried += again.size();
 		GaLaunch Rl = L;
 		uint32_t maxRows = 0;
 		for (uint32_t i : again) maxRows = std::max(maxRows, jobs[i].n_rows);
-		Rl.cap_cols = capCols;
-		Rl.trace_cap = maxRows * traceMul + 4096;
+		Rl.cap_cols = geo.capCols;
+		Rl.trace_cap = maxRows * geo.traceMul + 4096;
 		Rl.max_slices = std::max<uint32_t>(maxRows / 64, 1);
-		Rl.arena_words = std::min<uint64_t>(64 + (uint64_t)(maxRows / 64) * (gak::kSliceHdrWords + arenaWordsPerSlice) + arenaWordsExtra, 0xfffffff0ull);
-		Rl.sparse_bw = SPARSE ? (uint32_t)std::max(std::max(L.initial_bw, L.ramp_bw), 1) : 0u;
-		SlotLayout lay = slotLayout(Rl.cap_cols, Rl.max_slices, Rl.arena_words, Rl.trace_cap, Rl.sparse_bw, kWide ? sizeof(gak::WaveState<MAXN>) : 0, MAXN);
+		Rl.arena_words = std::min<uint64_t>(64 + (uint64_t)(maxRows / 64) * (gak::kSliceHdrWords + geo.arenaWordsPerSlice) + geo.arenaWordsExtra, 0xfffffff0ull);
+		Rl.sparse_bw = k.sparseNodes ? (uint32_t)std::max(std::max(L.initial_bw, L.ramp_bw), 1) : 0u;
+		SlotLayout lay = slotLayout(Rl.cap_cols, Rl.max_slices, Rl.arena_words, Rl.trace_cap, Rl.sparse_bw, k.stateBytes, k.maxN);
+		const uint64_t sparseBytes = k.sparseNodes > 256 ? gak::sparse_mem_bytes<kWideNodes>(Rl.sparse_bw) : k.sparseNodes ? gak::sparse_mem_bytes<256>(Rl.sparse_bw) : 0;
 		Rl.slot_bytes = lay.bytes;
 		const uint64_t fit = scratchBudget() / lay.bytes;
-		uint32_t rslots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((uint64_t)g->cus * wavesPerCuRetry, fit), again.size()));
-		if (kWide && SPARSE) rslots = std::min(rslots, kWideSparseSlots);
+		uint32_t rslots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((uint64_t)g->cus * geo.wavesPerCu, fit), again.size()));
+		if (geo.slotCap) rslots = std::min(rslots, geo.slotCap);
 		if (knobs.waveSlots) rslots = std::min(rslots, knobs.waveSlots);
 		bool fromPool = false;
 		uint8_t* scratch = takeScratch((size_t)rslots * lay.bytes, fromPool);
 		if (!scratch) return 0;                            // the affected jobs keep their capacity status
 		Rl.scratch = scratch;
-		if (passNo == 1) { st.slots = rslots; st.waves_per_cu = wavesPerCuRetry; st.scratch_bytes = (uint64_t)rslots * lay.bytes; }
+		if (passNo == 1) { st.slots = rslots; st.waves_per_cu = geo.wavesPerCu; st.scratch_bytes = (uint64_t)rslots * lay.bytes; }
 		Rl.job_list = dList;
 		Rl.n_jobs = (uint32_t)again.size();
 		int rc = uploadList(again);
 		if (!rc)
 		{
 			hipMemsetAsync(Rl.next_job, 0, 16, stream);
-			// (the sparse method's tables are generation-stamped: they start from zero once per launch)
-			if constexpr (kWide && SPARSE)
+			if (k.clearSlotBySlot)
 			{
-				// (slot by slot: the tables of this variant are some 160 MB of a 360 MB slot; without them cleared nothing is launched)
 				for (uint32_t s = 0; s < rslots && !rc; s++)
-					if (hipMemsetAsync(scratch + (uint64_t)s * lay.bytes + lay.sparse, 0, gak::sparse_mem_bytes<MAXN>(Rl.sparse_bw), stream) != hipSuccess) rc = GA_E_DEVICE;
+					if (hipMemsetAsync(scratch + (uint64_t)s * lay.bytes + lay.sparse, 0, sparseBytes, stream) != hipSuccess) rc = GA_E_DEVICE;
 			}
-			else if (SPARSE) hipMemset2DAsync(scratch + lay.sparse, lay.bytes, 0, gak::sparse_mem_bytes<MAXN>(Rl.sparse_bw), rslots, stream);
+			else if (k.sparseNodes) hipMemset2DAsync(scratch + lay.sparse, lay.bytes, 0, sparseBytes, rslots, stream);
 		}
 		if (!rc)
 		{
 			hipEventRecord(evA, stream);
-			if constexpr (kWide && SPARSE) hipLaunchKernelGGL(ga_wide_sparse_kernel, dim3(rslots), dim3(64), 0, stream, Rl);
-			else if constexpr (kWide) hipLaunchKernelGGL(ga_wide_kernel, dim3(rslots), dim3(64), 0, stream, Rl);
-			else hipLaunchKernelGGL((ga_extend_kernel<MAXN, GENERAL, SPARSE>), dim3(rslots), dim3(64), 0, stream, Rl);
+			hipLaunchKernelGGL(k.kernel, dim3(rslots), dim3(64), 0, stream, Rl);
 			float ms = 0;
 			rc = afterPass(ms);
 			if (knobs.debugPasses)
 			{
 				size_t capNodes = 0;
 				for (uint32_t i : again) if (outs[i].status == GA_CAP_NODES) capNodes++;
-				fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d%s>: %zu jobs on %u slots, %.2f ms, %zu left with GA_CAP_NODES\n", MAXN, (int)GENERAL, SPARSE ? ",sparse" : "", again.size(), rslots, ms, capNodes);
+				fprintf(stderr, "graphaligner_amd: wave-per-read pass <%d,%d%s>: %zu jobs on %u slots, %.2f ms, %zu left with GA_CAP_NODES\n", k.maxN, (int)k.general, k.sparseNodes ? ",sparse" : "", again.size(), rslots, ms, capNodes);
 			}
 		}
 		if (fromPool) g->givePool();
 		return rc;
+	}
+
+	// gald::climb's back end: the one place that names the kernels' template arguments
+#ifndef GA_FIRST_N
+#define GA_FIRST_N 32
+#endif
+	int launch(gald::Variant v, const std::vector<uint32_t>& list, bool first)
+	{
+		constexpr uint64_t kWideState = sizeof(gak::WaveState<kWideNodes>);
+		static_assert(gak::Limits<kWideNodes>::kStateInHbm && !gak::Limits<256>::kStateInHbm, "two variants keep their state in HBM: <4096,true> and <4096,true,true>");
+		const WaveGeom& geo = kWaveGeom[gald::isLanes(v) ? 0 : v - gald::kLean32];
+		switch (v)
+		{
+		case gald::kLanes10: return lanesPass<10, 64>(list, kLanesRowsPerSlice[0], first);
+		case gald::kLanes24: return lanesPass<24, 32>(list, kLanesRowsPerSlice[1], first);
+		case gald::kLanes56: return lanesPass<56, 16>(list, kLanesRowsPerSlice[2], first);
+		case gald::kLean32:
+		{
+			if (int rc = wavePass({ga_extend_kernel<GA_FIRST_N, false>, GA_FIRST_N, false, 0, 0, false}, geo, list)) return rc;
+			st.main_ms = st.kernel_ms;
+			st.main_variant = -GA_FIRST_N;                 // (negative: the wave-per-read kernel with that many band nodes in LDS)
+			return 0;
+		}
+		case gald::kLean64: return wavePass({ga_extend_kernel<64, false>, 64, false, 0, 0, false}, geo, list);
+		case gald::kGeneral64: return wavePass({ga_extend_kernel<64, true>, 64, true, 0, 0, false}, geo, list);
+		case gald::kGeneral256: return wavePass({ga_extend_kernel<256, true>, 256, true, 0, 0, false}, geo, list);
+		case gald::kWide: return wavePass({ga_wide_kernel, kWideNodes, true, kWideState, 0, false}, geo, list);
+		case gald::kSparse256: return wavePass({ga_extend_kernel<256, true, true>, 256, true, 0, 256, false}, geo, list);
+		case gald::kWideSparse: return wavePass({ga_wide_sparse_kernel, kWideNodes, true, kWideState, kWideNodes, true}, geo, list);
+		default: return GA_E_INVALID;
+		}
 	}
 
 	// ---- GA_F_OPS (ga_ops.h): after the last pass, every finished job's moves coded as runs where they lie -------------------------
@@ -1110,76 +1165,13 @@ struct DevBatch : GaBackendBatch
 		hipLaunchKernelGGL(ga_outs_init_kernel, dim3((uint32_t)((jobs.size() + 255) / 256)), dim3(256), 0, stream, L.outs, (uint32_t)jobs.size());
 		HIP_OK(hipGetLastError());
 		HIP_OK(hipMemsetAsync(L.trace_top, 0, 16, stream));
-		// ---- first the lanes = reads kernel: one job per lane.  Its LDS tables hold 16, 32 or 64 band nodes per lane (4, 2, 1
-		// waves per CU); the starting size follows the graph's mean node length, and jobs a size cannot hold move to the next ----
-		// It is the first pass where its lockstep pays: the lanes of a wave take their k-th band node together, so on graphs of long,
-		// equally long nodes (mean node length >= 40 bp: linear and sparsely branching graphs) every lane is busy; on graphs chopped
-		// into short uneven nodes the wave-per-read kernel is still the faster one and goes first.  GA_LANES=1 / 0 forces the choice.
+		// ---- the passes (ga_ladder.h): first the lanes = reads kernel, one job per lane, where the graph's shape makes its lockstep pay
+		// -- its LDS tables hold 10, 24 or 56 band nodes per lane, the starting size follows the graph's mean node length, and jobs a
+		// size cannot hold move to the next -- or the lean wave-per-read kernel; what is left climbs the wave-per-read rungs.
+		// GA_LANES=1 / 0 forces which kernel goes first. ----
 		const double meanNode = g->g.n_nodes > 2 ? (double)g->totalBp / (double)(g->g.n_nodes - 2) : 64.0;
-		const bool useLanes = knobs.lanes >= 0 ? knobs.lanes != 0 : meanNode >= 40;
-		int rc = 0;
-		if (useLanes)
-		{
-			const int startN = meanNode >= 40 ? 0 : meanNode >= 14 ? 1 : 2;
-			std::vector<uint32_t> list = orderHost;
-			bool first = true;
-			for (int n = startN; n <= 2 && !list.empty() && !rc; n++)
-			{
-				// later sizes are only worth a launch of their own for enough jobs to fill waves; stragglers take the wave-per-read ladder
-				if (!first && list.size() < 512) break;
-				// (10 / 24 / 56 band nodes per lane = 4 / 2 / 1 waves per CU next to the 12.8 KB block image)
-				// (rows per lane and slice: the band's columns rounded up to blocks of 8 per node, with room for the widest slices)
-				if (n == 0) rc = lanesPass<10, 64>(list, 288, first);
-				// (the wider tables trade lanes for LDS per lane: 32 and 16 lanes per wave keep four waves on every CU -- the same number of
-				// reads in flight as 64-lane waves that leave three SIMDs of four idle, in four times as many instruction streams)
-				else if (n == 1) rc = lanesPass<24, 32>(list, 480, first);
-				else rc = lanesPass<56, 16>(list, 768, first);
-				first = false;
-				std::vector<uint32_t> again;
-				for (uint32_t i : list) if (widerLanes(outs[i].status)) again.push_back(i);
-				list.swap(again);
-			}
-			if (rc) return rc;
-		}
-		// ---- what is left climbs the wave-per-read ladder: 64 band nodes in LDS; then the general variants, which also carry the
-		// paths for bands with cycles and for ramp redos; last 256 band nodes with large buffers ----
-		st.jobs_retried = 0;
-		if (!useLanes)
-		{
-			// the lean wave-per-read variant over everything (32 band nodes in LDS, 24 waves per CU)
-#ifndef GA_FIRST_N
-#define GA_FIRST_N 32
-#endif
-			rc = retryPass<GA_FIRST_N, false>(4096, 3 * 64 + 5 * 800, 2, 24, true, false);
-			if (rc) return rc;
-			st.main_ms = st.kernel_ms;
-			st.main_variant = -GA_FIRST_N;                 // (negative: the wave-per-read kernel with that many band nodes in LDS)
-			st.jobs_retried = 0;
-		}
-		rc = retryPass<64, false>(8192, 3 * 64 + 5 * 2048, 3, 12, true, false);
-		if (rc) return rc;
-		rc = retryPass<64, true>(8192, 3 * 64 + 5 * 4096, 4, 8, false, true);      // only what needs the extra paths: capacity misses go straight on
-		if (rc) return rc;
-		rc = retryPass<256, true>(65536, 3 * 256 + 5 * 8192, 6, 4, true, true);
-		if (rc) return rc;
-		// bit-vector bands of more than 256 nodes (tangles of short nodes, wide bubbles, fans): 4 096 band nodes with the tables in HBM,
-		// one wave per CU, only for the jobs that overflowed the band tables or the projection heap.  A bit-vector band has at most
-		// 199 999 columns.  Arena per slice: the node table of 4 096 nodes and 32 768 columns -- four times the figure of the pass
-		// before for sixteen times its nodes, because what overflows 256 band nodes is short nodes (the passes before allow 32 columns
-		// per table node; 8 per node here), and few slices of a job are that wide.  A job that needs more reports GA_CAP_ARENA and
-		// goes on to the last pass like every other capacity miss.
-		rc = retryPass<kWideNodes, true>(kCutoffCols, 3 * (uint64_t)kWideNodes + 5 * 32768, 8, 1, true, true);
-		if (rc) return rc;
-		// bands of 200 000 cells and more (the reference's sparse method and backtrace override, ga_sparse.h): a fallback, run for the
-		// jobs that met such a band, with room for every column of every node such a slice touches
-		// (also the last resort for what the passes before could not hold: bit-vector bands may have up to 199 999 columns)
-		rc = retryPass<256, true, true>(1u << 20, 3 * 256 + 5 * 20000, 8, 1, true, true, 48ull << 20);
-		if (rc) return rc;
-		// such bands with more than 256 nodes (fans and tangles of hundreds to thousands of nodes): the same with 4 096 band nodes, the
-		// state in HBM and tables sized for it, only for the jobs the pass above left with GA_CAP_NODES -- the other capacity misses of
-		// that pass (its row set, its touched columns, the arena, the trace) keep their status.  Arena as above: room for every column
-		// of every node a sparse slice touches, 2^20 columns.  No such job, no launch.
-		rc = retryPass<kWideNodes, true, true>(1u << 20, 3 * (uint64_t)kWideNodes + 5 * 20000, 8, 1, true, true, 48ull << 20);
+		const int rc = gald::climb(orderHost, outs, passOf, passNo, st.jobs_retried, gald::firstPassFor(meanNode, knobs.lanes),
+		                           [&](gald::Variant v, const std::vector<uint32_t>& list, bool first) { return launch(v, list, first); });
 		for (int k = 0; k < 8; k++) { st.stamps[k] = 0; for (auto& o : outs) st.stamps[k] += o.stamps[k]; }
 		return rc;
 	}

@@ -281,3 +281,21 @@ def fan_batch():
     seeds = seeds + [seeds[2]]
     oras = pc.oracle_results(g.nodes, g.edges, out, seeds, bw, ramp)
     return g, out, seeds, oras
+
+
+def case_sparse_variant_sees_the_alphabet(trace, lib_path=None):
+    """fan_batch's reads against the oracle alone (no model of a fan); no part whose oracle run shows a sparse slice was finished by the
+    first pass.  -> (results, oracle results, the number of such parts that align)"""
+    g, reads, seeds, oras = fan_batch()
+    bw, ramp = FAN[4], FAN[5]
+    assert sum(1 for o in oras if o["status"] == 0 and not o["failed"]) >= 4 and any(o["status"] == 1 for o in oras)
+    need = sum(1 for o in oras if o["sparse_slices"] > 0 and o["status"] == 0)
+    assert need >= 4, need
+    gg = binding.Graph(g.nodes, g.edges, lib_path=lib_path)
+    b = gg.prepare(reads, [[s] for s in seeds], bw, ramp, binding.GA_F_TRACE if trace else 0)
+    b.run()
+    devs = b.collect()
+    for i, (d, o) in enumerate(zip(devs, oras)):
+        pc.compare_read(d, pc.expected(o, trace), "fan read %d with ambiguity codes" % i)
+    assert all(d["kernel_pass"] > 0 for d, o in zip(devs, oras) if o["sparse_slices"] > 0 and o["status"] == 0), [d["kernel_pass"] for d in devs]
+    return devs, oras, need

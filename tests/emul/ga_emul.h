@@ -4,7 +4,7 @@
 // ga_wave_emul.h, and what the product does by a kernel launch is a loop over the launch's items here.  One graph, one batch and one
 // seed engine, split over a few files by subject:
 //   ga_emul_backend.cpp  the graph and the batch, the switch below, the match words
-//   ga_emul_ladder.cpp   EmulBatch::climb: the lanes = reads passes and the wave-per-read ladder
+//   ga_emul_ladder.cpp   EmulBatch::climb and launch: the passes of the product's ladder (ga_ladder.h), each a loop over its jobs
 //   ga_emul_seed.cpp     the seed engine
 //   ga_emul_plan.cpp     EmulGraph::beginSeededBatch: the plan of a seeded batch
 //   ga_emul_ops.cpp      EmulBatch::codeOps: the operations of GA_F_OPS
@@ -15,10 +15,13 @@
 #include <vector>
 
 #include "../../graphaligner_amd/csrc/ga_backend.h"
+#include "../../graphaligner_amd/csrc/ga_ladder.h"
 
 namespace gae {
 
-// With nothing set the back end does what the product's does.  GA_EMUL_WITHOUT, read at every ga_backend_upload_graph, is a comma-separated
+// With nothing set the back end does what the product's does: the same passes over the same jobs (ga_ladder.h), with two intended
+// differences -- its capacities are its own, and its first pass does not follow the graph's shape (GA_LANES=0: the wave-per-read
+// kernel first; else the lanes = reads kernel, always from <10,64>, every later size for any number of jobs).  GA_EMUL_WITHOUT, read at every ga_backend_upload_graph, is a comma-separated
 // list of capabilities that the graph and its batches withhold; a withheld capability answers what the interface's base class answers
 // (ga_backend.h), so the tests can see how the host code and the Python layers behave in front of a back end that lacks it.
 enum : uint32_t
@@ -62,9 +65,9 @@ struct EmulBatch : GaBackendBatch
 	std::vector<GaJobOut> outs;
 	std::vector<uint8_t> pool;
 	uint64_t poolTop = 0;
-	uint64_t lanesDone = 0, retried = 0;
-	uint64_t wide = 0;         // jobs handed to <4096,true>
-	uint64_t wideSparse = 0;   // jobs handed to <4096,true,true>
+	std::vector<uint8_t> passOf;   // which pass of the last run finished each job (0 = the first)
+	int passNo = 0;
+	uint64_t retried = 0;
 
 	bool seeded = false;       // made by beginSeededBatch: finishSeeded brings the jobs
 
@@ -83,11 +86,12 @@ struct EmulBatch : GaBackendBatch
 	uint64_t opsJobs = 0, opsMoves = 0;
 	double opsMs = 0;
 
-	// ga_emul_ladder.cpp: all passes over the jobs, as DevBatch::run makes them
+	// ga_emul_ladder.cpp: all passes over the jobs, as DevBatch::run makes them -- climb hands the product's policy launch as its back end
 	bool poison = false, reuse = false;
 	KeptBuffers* kept = nullptr;
 	template <int MAXN, bool GENERAL, bool SPARSE = false> void runOne(uint32_t job, uint32_t capCols, uint64_t arenaWords, uint32_t traceCap);
 	template <int N> void runLanesGroup(const std::vector<uint32_t>& group, uint32_t capCols, uint32_t capRows, uint32_t capMoves);
+	int launch(gald::Variant v, const std::vector<uint32_t>& list, bool first);
 	void climb();
 	// ga_emul_ops.cpp: the two launches of ga_ops.h behind the last pass
 	void codeOps();
@@ -104,6 +108,7 @@ struct EmulBatch : GaBackendBatch
 	int fetch(std::vector<GaJobOut>& o, const uint8_t** traces, uint64_t* nBytes) override
 	{
 		o = outs;
+		for (size_t i = 0; i < o.size(); i++) o[i].reserved2 = passOf[i];      // 0 = finished by the first pass
 		*traces = pool.data();
 		*nBytes = poolTop;
 		return 0;

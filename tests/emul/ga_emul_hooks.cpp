@@ -1,5 +1,6 @@
 // ga_emul_hooks.cpp -- TEST-ONLY (ga_emul.h): component hooks for unit tests of pieces of graphaligner_amd/csrc/ga_kernel.h, ga_sparse.h
-// and ga_lanes.h, each run on the host with the wave primitives of ga_wave_emul.h.
+// and ga_lanes.h, each run on the host with the wave primitives of ga_wave_emul.h, and of the ladder's policy (ga_ladder.h).
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <unordered_map>
@@ -7,6 +8,7 @@
 
 #include "../../graphaligner_amd/csrc/ga_backend.h"
 #include "../../graphaligner_amd/csrc/ga_kernel.h"
+#include "../../graphaligner_amd/csrc/ga_ladder.h"
 #include "../../graphaligner_amd/csrc/ga_lanes.h"
 
 // component hooks for unit tests of the order-emulation pieces
@@ -178,3 +180,32 @@ extern "C" void ga_emul_wide_sparse_limits(uint32_t* out)
 }
 // bytes of the 256 variant's sparse tables at a bandwidth (its layout is pinned: 256 + the six regions of DESIGN.md section 4b)
 extern "C" uint64_t ga_emul_wide_sparse_mem_bytes(int nodes, uint32_t bw) { return nodes > 256 ? gak::sparse_mem_bytes<4096>(bw) : gak::sparse_mem_bytes<256>(bw); }
+
+// ---- the ladder's policy (ga_ladder.h) over a scripted back end: n jobs in index order, and after[v * n + j] = the status job j has
+// after variant v ran it.  Out: per launch [variant, first, list size], the lists one after the other (at most gald::kVariants * n
+// entries), passOf per job, the retried count.  Returns the number of launches.
+extern "C" int ga_emul_ladder_climb(int n, int lanesFirst, int startLanes, uint32_t minJobsLater, const int32_t* after, int32_t* launches, uint32_t* lists, uint8_t* passOf, uint64_t* retried)
+{
+	std::vector<uint32_t> order(n);
+	for (int i = 0; i < n; i++) order[i] = (uint32_t)i;
+	std::vector<GaJobOut> outs(n, GaJobOut{});
+	for (auto& o : outs) o.status = GA_NOT_RUN;
+	std::vector<uint8_t> of(n, 0);
+	int passNo = 0, nLaunches = 0;
+	size_t at = 0;
+	gald::climb(order, outs, of, passNo, *retried, gald::FirstPass{lanesFirst != 0, (gald::Variant)startLanes, minJobsLater},
+	            [&](gald::Variant v, const std::vector<uint32_t>& list, bool first) {
+		launches[3 * nLaunches] = v; launches[3 * nLaunches + 1] = first; launches[3 * nLaunches + 2] = (int32_t)list.size();
+		nLaunches++;
+		for (uint32_t j : list) { lists[at++] = j; outs[j].status = after[(size_t)v * n + j]; }
+		return 0;
+	});
+	std::copy(of.begin(), of.end(), passOf);
+	return nLaunches == passNo ? nLaunches : -1;
+}
+// the product's first pass for a graph's mean node length and GA_LANES (1 / 0, negative: unset): [lanes first, starting size, minJobsLater]
+extern "C" void ga_emul_ladder_first_pass(double meanNodeLength, int forced, int32_t* out)
+{
+	const gald::FirstPass fp = gald::firstPassFor(meanNodeLength, forced);
+	out[0] = fp.lanesFirst; out[1] = fp.startLanes; out[2] = (int32_t)fp.minJobsLater;
+}

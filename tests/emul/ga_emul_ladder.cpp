@@ -1,9 +1,8 @@
 // ga_emul_ladder.cpp -- TEST-ONLY (ga_emul.h): the device extension program of graphaligner_amd/csrc/ga_kernel.h and the lanes = reads
-// program of ga_lanes.h run on the host, every wave64 primitive emulated by ga_wave_emul.h, one job after the other, through the passes
-// of DevBatch::run: the three lanes variants, <32,false>, <64,true>, <256,true>, then run_job<4096,true> for the jobs that <256,true>
-// left with GA_CAP_NODES or GA_CAP_HEAP (as ga_wide_kernel), <256,true,true> for GA_UNSUPPORTED_BAND and behind it run_job<4096,true,true>
-// for the jobs that it left with GA_CAP_NODES and for no others (as ga_wide_sparse_kernel).  The two passes with 4 096 band nodes can
-// be withheld (GA_EMUL_WITHOUT=wide,wide_sparse): the tests compare the ladders.
+// program of ga_lanes.h run on the host, every wave64 primitive emulated by ga_wave_emul.h, through the passes of DevBatch::run.  Which
+// variant runs over which jobs, and in which order, is the product's policy (graphaligner_amd/csrc/ga_ladder.h, gald::climb); what is
+// the emulation's own is EmulBatch::launch -- a loop over the pass's jobs, with capacities of its own -- and how a batch starts (see
+// climb below).  The two passes with 4 096 band nodes can be withheld (GA_EMUL_WITHOUT=wide,wide_sparse): the tests compare the ladders.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +11,7 @@
 
 #include "ga_emul.h"
 #include "../../graphaligner_amd/csrc/ga_kernel.h"
+#include "../../graphaligner_amd/csrc/ga_ladder.h"
 #include "../../graphaligner_amd/csrc/ga_lanes.h"
 
 namespace {
@@ -164,92 +164,93 @@ template <int N> void EmulBatch::runLanesGroup(const std::vector<uint32_t>& grou
 	for (int lane = 0; lane < 64; lane++) lane_finish<N>(L, mem[lane], st[lane], lane < (int)group.size());
 }
 
+// The emulation's own geometry: deliberately small capacities in the early rungs, so that small test batches climb the ladder too.
+// lanes = reads variants: a group's arena rows = slices of its longest job * rowsMul + 64, its moves = rows * movesMul + 512
+struct LanesGeom { uint32_t capCols, rowsMul, movesMul; };
+constexpr LanesGeom kLanesGeom[] = {{2048, 600, 2}, {4096, 2500, 3}, {8192, 2500, 3}};
+// wave-per-read rungs, in the order of gald::kRungs, per job: arena words = 64 + slices * (kSliceHdrWords + arenaWordsPerSlice) *
+// arenaMul, trace bytes = rows * traceMul + traceAdd
+struct WaveGeom { uint32_t capCols; uint64_t arenaWordsPerSlice; uint32_t arenaMul, traceMul, traceAdd; };
+constexpr WaveGeom kWaveGeom[] = {
+	{2048, 3 * 40 + 5 * 700, 1, 2, 512},             // <32,false>
+	{4096, 3 * 64 + 5 * 1500, 1, 3, 1024},           // <64,false>
+	{4096, 3 * 64 + 5 * 1500, 2, 3, 1024},           // <64,true>
+	{200000, 3 * 256 + 5 * 20000, 3, 8, 4096},       // <256,true>
+	{200000, 3 * 4096 + 5 * 32768, 1, 8, 4096},      // <4096,true>: a bit-vector band of more than 256 nodes, or a projection heap of more than 1 024 entries
+	{2000000, 3 * 256 + 6 * 300000, 1, 8, 4096},     // <256,true,true>: a band of 200 000 cells or more (ga_sparse.h)
+	{2000000, 3 * 4096 + 6 * 300000, 1, 8, 4096},    // <4096,true,true>
+};
+static_assert(sizeof(kWaveGeom) / sizeof(kWaveGeom[0]) == sizeof(gald::kRungs) / sizeof(gald::kRungs[0]), "one geometry per wave-per-read rung");
+
+// what a kernel launch over `list` is on the device: the lanes = reads program over groups of 64 jobs, the wave-per-read program
+// over one job after the other
+int EmulBatch::launch(gald::Variant v, const std::vector<uint32_t>& list, bool)
+{
+	if (getenv("GA_EMUL_DEBUG")) fprintf(stderr, "emul: pass %d, variant %d: %zu jobs\n", passNo - 1, (int)v, list.size());
+	if (gald::isLanes(v))
+	{
+		const LanesGeom& geo = kLanesGeom[v];
+		for (size_t at = 0; at < list.size(); at += 64)
+		{
+			std::vector<uint32_t> group(list.begin() + at, list.begin() + std::min(list.size(), at + 64));
+			const uint32_t maxRows = jobs[group[0]].n_rows;
+			const uint32_t capRows = (maxRows / 64) * geo.rowsMul + 64, capMoves = maxRows * geo.movesMul + 512;
+			if (v == gald::kLanes10) runLanesGroup<10>(group, geo.capCols, capRows, capMoves);
+			else if (v == gald::kLanes24) runLanesGroup<24>(group, geo.capCols, capRows, capMoves);
+			else runLanesGroup<56>(group, geo.capCols, capRows, capMoves);
+		}
+		return 0;
+	}
+	if ((v == gald::kWide && (g->without & NO_WIDE)) || (v == gald::kWideSparse && (g->without & NO_WIDE_SPARSE))) return 0;
+	if (v == gald::kWideSparse) gLastWideSparse = list.size();
+	if (rows.empty()) rows = rowsProvider();         // the wave-per-read kernels read the row codes
+	const WaveGeom& geo = kWaveGeom[v - gald::kLean32];
+	for (uint32_t j : list)
+	{
+		const uint64_t arenaWords = 64 + (uint64_t)(jobs[j].n_rows / 64) * (gak::kSliceHdrWords + geo.arenaWordsPerSlice) * geo.arenaMul;
+		const uint32_t traceCap = jobs[j].n_rows * geo.traceMul + geo.traceAdd;
+		switch (v)
+		{
+		case gald::kLean32: runOne<32, false>(j, geo.capCols, arenaWords, traceCap); break;
+		case gald::kLean64: runOne<64, false>(j, geo.capCols, arenaWords, traceCap); break;
+		case gald::kGeneral64: runOne<64, true>(j, geo.capCols, arenaWords, traceCap); break;
+		case gald::kGeneral256: runOne<256, true>(j, geo.capCols, arenaWords, traceCap); break;
+		case gald::kWide: runOne<4096, true>(j, geo.capCols, arenaWords, traceCap); break;
+		case gald::kSparse256: runOne<256, true, true>(j, geo.capCols, arenaWords, traceCap); break;
+		default: runOne<4096, true, true>(j, geo.capCols, arenaWords, traceCap); break;
+		}
+	}
+	return 0;
+}
+
 void EmulBatch::climb()
 {
 	outs.assign(jobs.size(), GaJobOut{});
+	for (auto& o : outs) o.status = GA_NOT_RUN;
 	uint64_t totalRows = 0;
 	for (auto& j : jobs) totalRows += j.n_rows;
 	pool.assign(totalRows * 3 + 4096 * jobs.size() + 64, 0);
 	if (const char* t = getenv("GA_TEST_TRACE_POOL_BYTES")) pool.assign((size_t)atoll(t) & ~(size_t)3, 0);
 	poolTop = 0;
-	retried = 0;
-	wide = 0;
-	wideSparse = 0;
+	gLastWideSparse = 0;
 	poison = envOn("GA_EMUL_POISON");
 	reuse = envOn("GA_EMUL_REUSE");
 	KeptBuffers buffers;
 	kept = &buffers;
-	// first pass: the lanes = reads program, groups of 64 jobs (longest first, as the device queue hands them out), with
-	// deliberately small capacities; what it declines or cannot hold climbs the wave-per-read ladder below
-	const bool lanesFirst = !(getenv("GA_EMUL_NO_LANES") && atoi(getenv("GA_EMUL_NO_LANES")));
-	if (lanesFirst)
-	{
-		// jobs a lanes variant cannot hold (band wider than its LDS tables) move on to the next one, regrouped
-		std::vector<uint32_t> order(jobs.size());
-		for (uint32_t i = 0; i < jobs.size(); i++) order[i] = i;
-		std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].n_rows > jobs[b].n_rows; });
-		for (int pass = 0; pass < 3 && !order.empty(); pass++)
-		{
-			for (size_t at = 0; at < order.size(); at += 64)
-			{
-				std::vector<uint32_t> group(order.begin() + at, order.begin() + std::min(order.size(), at + 64));
-				const uint32_t maxRows = jobs[group[0]].n_rows;
-				const uint32_t capRows = (maxRows / 64) * (pass == 0 ? 600 : 2500) + 64, capMoves = maxRows * (pass == 0 ? 2 : 3) + 512;
-				if (pass == 0) runLanesGroup<10>(group, 2048, capRows, capMoves);
-				else if (pass == 1) runLanesGroup<24>(group, 4096, capRows, capMoves);
-				else runLanesGroup<56>(group, 8192, capRows, capMoves);
-			}
-			std::vector<uint32_t> again;
-			for (uint32_t j : order) if (outs[j].status == GA_CAP_NODES || outs[j].status == GA_CAP_HEAP || outs[j].status == GA_CAP_COLS || outs[j].status == GA_CAP_ARENA || outs[j].status == GA_CAP_TRACE) again.push_back(j);
-			if (getenv("GA_EMUL_DEBUG")) fprintf(stderr, "emul: lanes pass %d: %zu jobs, %zu move on\n", pass, order.size(), again.size());
-			order.swap(again);
-		}
-	}
-	lanesDone = 0;
-	if (rows.empty()) rows = rowsProvider();         // the wave-per-read kernels below read the row codes
-	if (getenv("GA_EMUL_DEBUG") && lanesFirst) { int hist[100] = {0}; for (auto& o : outs) hist[o.status < 100 ? o.status : 99]++; fprintf(stderr, "emul: lanes statuses:"); for (int i = 0; i < 100; i++) if (hist[i]) fprintf(stderr, " %d:%d", i, hist[i]); fprintf(stderr, "\n"); }
-	// a band of 200 000 cells or more: the variant that carries the sparse method and the backtrace override (ga_sparse.h), and behind
-	// it, only for a job that variant left with GA_CAP_NODES, the same with 4 096 band nodes
-	auto sparsePasses = [&](uint32_t j, uint32_t slices) {
-		retried++;
-		runOne<256, true, true>(j, 2000000, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 256 + 6 * 300000), jobs[j].n_rows * 8 + 4096);
-		if (getenv("GA_EMUL_DEBUG")) fprintf(stderr, "emul: job %u: status %d after <256,true,true>\n", j, outs[j].status);
-		if (outs[j].status != GA_CAP_NODES || (g->without & NO_WIDE_SPARSE)) return;
-		wideSparse++;
-		runOne<4096, true, true>(j, 2000000, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 4096 + 6 * 300000), jobs[j].n_rows * 8 + 4096);
-		if (getenv("GA_EMUL_DEBUG")) fprintf(stderr, "emul: job %u: status %d after <4096,true,true>\n", j, outs[j].status);
-	};
-	for (uint32_t j = 0; j < jobs.size(); j++)
-	{
-		uint32_t slices = jobs[j].n_rows / 64;
-		auto finalStatus = [](int s) { return s == GA_OK || s == GA_ASSERTION || s == GA_BAD_SEED; };
-		if (lanesFirst && finalStatus(outs[j].status)) { lanesDone++; continue; }
-		if (lanesFirst && outs[j].status == GA_UNSUPPORTED_BAND)
-		{
-			sparsePasses(j, slices);
-			continue;
-		}
-		// deliberately small first-try capacities so the retry ladder is exercised too
-		runOne<32, false>(j, 2048, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 40 + 5 * 700), jobs[j].n_rows * 2 + 512);
-		auto capacity = [](int s) { return s == GA_CAP_NODES || s == GA_CAP_COLS || s == GA_CAP_ARENA || s == GA_CAP_TRACE || s == GA_CAP_HEAP; };
-		auto general = [](int s) { return s == GA_UNSUPPORTED_CYCLE || s == GA_UNSUPPORTED_RAMP; };
-		if (capacity(outs[j].status) || general(outs[j].status)) retried++;
-		if (general(outs[j].status))
-			runOne<64, true>(j, 4096, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 64 + 5 * 1500) * 2, jobs[j].n_rows * 3 + 1024);
-		if (capacity(outs[j].status) || general(outs[j].status))
-			runOne<256, true>(j, 200000, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 256 + 5 * 20000) * 3, jobs[j].n_rows * 8 + 4096);
-		// a bit-vector band of more than 256 nodes, or a projection heap of more than 1 024 entries: 4 096 band nodes
-		if ((outs[j].status == GA_CAP_NODES || outs[j].status == GA_CAP_HEAP) && !(g->without & NO_WIDE))
-		{
-			wide++;
-			runOne<4096, true>(j, 200000, 64 + (uint64_t)slices * (gak::kSliceHdrWords + 3 * 4096 + 5 * 32768), jobs[j].n_rows * 8 + 4096);
-		}
-		if (outs[j].status == GA_UNSUPPORTED_BAND) sparsePasses(j, slices);
-	}
+	// the hand-out order of the device queues: longest first
+	std::vector<uint32_t> order(jobs.size());
+	for (uint32_t i = 0; i < jobs.size(); i++) order[i] = i;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].n_rows > jobs[b].n_rows; });
+	passOf.assign(jobs.size(), 0);
+	passNo = 0;
+	// the emulation's first pass: GA_LANES as the product reads it, but with no choice by the graph's shape (unset: lanes first), the lanes
+	// sizes always from <10,64>, and a later size for any number of jobs, so that small test batches still reach all three
+	const char* e = getenv("GA_LANES");
+	const gald::FirstPass fp = {!(e && atoi(e) == 0), gald::kLanes10, 0};
+	gald::climb(order, outs, passOf, passNo, retried, fp, [&](gald::Variant v, const std::vector<uint32_t>& list, bool first) { return launch(v, list, first); });
 	if (getenv("GA_EMUL_DEBUG") && (poison || reuse)) fprintf(stderr, "emul: poison %d, reuse %d\n", (int)poison, (int)reuse);
 	kept = nullptr;
-	gLastWideSparse = wideSparse;
-	if (getenv("GA_EMUL_DEBUG")) { int hist[100] = {0}; for (auto& o : outs) hist[o.status < 100 ? o.status : 99]++; fprintf(stderr, "emul: %zu jobs, %llu finished by the lanes program, %llu retried, %llu by <4096,true>, %llu by <4096,true,true>; final statuses:", jobs.size(), (unsigned long long)lanesDone, (unsigned long long)retried, (unsigned long long)wide, (unsigned long long)wideSparse); for (int i = 0; i < 100; i++) if (hist[i]) fprintf(stderr, " %d:%d", i, hist[i]); fprintf(stderr, "\n"); }
+	if (getenv("GA_EMUL_DEBUG")) { int hist[100] = {0}; for (auto& o : outs) hist[o.status < 100 ? o.status : 99]++; fprintf(stderr, "emul: %zu jobs, %d passes, %llu retried, %llu by <4096,true,true>; final statuses:", jobs.size(), passNo, (unsigned long long)retried, (unsigned long long)gLastWideSparse); for (int i = 0; i < 100; i++) if (hist[i]) fprintf(stderr, " %d:%d", i, hist[i]); fprintf(stderr, "\n"); }
 }
 
 }  // namespace gae

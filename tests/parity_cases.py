@@ -398,6 +398,8 @@ def case_sparse_method_and_override(branches, branch_len, shared, stem, bw, ramp
         # reported, not asserted: these reads carry 3 % errors per kind and hardly ever go back (the redos that land on sparse
         # slices are redo_sparse_cases.py's)
         print("fan %d x %d bw%d/%d: the oracle saw %d redos, %d of them landing on a sparse slice" % ((branches, branch_len, bw, ramp) + _fan_redos(branches, branch_len, shared, stem, bw, ramp)))
+    # (such jobs are finished by the last kernels of the ladder, never by the first pass)
+    assert all(d["kernel_pass"] > 0 for d, o in zip(devs, oras) if o["sparse_slices"] > 0), [d["kernel_pass"] for d in devs]
     return devs, oras
 
 

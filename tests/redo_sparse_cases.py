@@ -147,6 +147,11 @@ def one_wave_batch(fan_index):
     return (fan, g) + tuple([x[i] for i in keep] for x in (reads, seeds, descs, oras, classes))
 
 
+def check_sparse_reads_climbed(devs, oras):
+    """no read whose oracle run shows a sparse slice was finished by the first pass"""
+    assert all(d["kernel_pass"] > 0 for d, o in zip(devs, oras) if o["sparse_slices"] > 0), [d["kernel_pass"] for d in devs]
+
+
 def sparse_parts(oras):
     """the parts (jobs) of a batch whose oracle run shows a sparse-method slice; every read here has one part (seed at its first base)"""
     return sum(1 for o in oras if o["sparse_slices"] > 0)

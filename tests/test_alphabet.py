@@ -4,8 +4,7 @@ sets of alphabet_cases.py through the host emulation of the device program.
 The emulation runs here with its own match words withheld (profile "emul" of parity_common.PROFILES: it takes the finished words and
 ignores GaEqSource), so what runs are the two host restatements of the rule: the match-word builder of ga_batch_prepare feeds the
 lanes = reads program, buildRows feeds the wave-per-read ladder.  GA_LANES chooses the first pass of the
-product; the emulation's name for the same choice is GA_EMUL_NO_LANES, and the fixture sets both, so that with the ladder first
-every job takes its rows from buildRows.  The kernel's own statement of the rule is test_alphabet_gpu.py's.
+product and of the emulation, so that with the ladder first every job takes its rows from buildRows.  The kernel's own statement of the rule is test_alphabet_gpu.py's.
 """
 import pytest
 
@@ -97,13 +96,19 @@ def test_model_says_something():
 @pytest.mark.parametrize("lanes", ["0", "1"], ids=["ladder-first", "lanes-first"])
 def test_probes_on_the_emulation(lib, name, lanes, trace, monkeypatch):
     monkeypatch.setenv("GA_LANES", lanes)
-    monkeypatch.setenv("GA_EMUL_NO_LANES", "1" if lanes == "0" else "0")
     ac.case_probes(name, ac.all_probes(), trace, lib)
 
 
 def test_node_runs_see_the_alphabet_on_the_emulation(lib, monkeypatch):
-    monkeypatch.delenv("GA_EMUL_NO_LANES", raising=False)
+    monkeypatch.delenv("GA_LANES", raising=False)
     ac.case_node_runs_see_the_alphabet(lib)
+
+
+@pytest.mark.parametrize("trace", [True, False], ids=["trace-items", "flags-0"])
+def test_sparse_variant_sees_the_alphabet_on_the_emulation(lib, trace, monkeypatch):
+    """ambiguity codes, lower case and one invalid byte inside the branches of a fan whose bands take the sparse method"""
+    monkeypatch.delenv("GA_LANES", raising=False)
+    ac.case_sparse_variant_sees_the_alphabet(trace, lib)
 
 
 def _expected_codes():

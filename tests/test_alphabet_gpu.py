@@ -12,8 +12,6 @@ import pytest
 
 import alphabet_cases as ac
 import parity_cases as cases
-import parity_common as pc
-from graphaligner_amd import binding
 
 pytestmark = pytest.mark.gpu
 
@@ -71,20 +69,10 @@ def test_more_fills_than_blocks():
 def test_sparse_variant_sees_the_alphabet(trace, capfd):
     """ambiguity codes, lower case and one invalid byte inside the branches of case_sparse_method_and_override's first fan: against the
     oracle alone (no model of a fan), and the sparse variant must have taken the parts whose oracle run shows a sparse slice"""
-    g, reads, seeds, oras = ac.fan_batch()
-    bw, ramp = ac.FAN[4], ac.FAN[5]
-    assert sum(1 for o in oras if o["status"] == 0 and not o["failed"]) >= 4 and any(o["status"] == 1 for o in oras)
-    need = sum(1 for o in oras if o["sparse_slices"] > 0 and o["status"] == 0)
-    assert need >= 4, need
+    ac.fan_batch()              # (its oracle runs print nothing into the capture below)
     capfd.readouterr()
-    gg = binding.Graph(g.nodes, g.edges)
-    b = gg.prepare(reads, [[s] for s in seeds], bw, ramp, binding.GA_F_TRACE if trace else 0)
-    b.run()
-    devs = b.collect()
+    need = ac.case_sparse_variant_sees_the_alphabet(trace)[2]
     err = capfd.readouterr().err
     print(err, end="")
-    for i, (d, o) in enumerate(zip(devs, oras)):
-        pc.compare_read(d, pc.expected(o, trace), "fan read %d with ambiguity codes" % i)
     lines = cases.passes_of(cases.debug_passes(err), SPARSE)
     assert max(p[1] for p in lines) >= need, (lines, need)
-    assert all(d["kernel_pass"] > 0 for d, o in zip(devs, oras) if o["sparse_slices"] > 0 and o["status"] == 0), [d["kernel_pass"] for d in devs]

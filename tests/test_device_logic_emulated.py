@@ -13,6 +13,17 @@ def lib():
     return pc.emul_lib_path()
 
 
+# Every case runs twice, as in tests/test_gpu_parity.py (the emulation has no choice by graph shape): here with the lanes = reads program
+# as the first pass (jobs it declines climb the wave-per-read ladder from <64,false>), and in test_device_logic_emulated_wave_first.py,
+# which takes over this module's tests and sets GA_LANES_FIRST = "0", with <32,false> over everything first.
+GA_LANES_FIRST = "1"
+
+
+@pytest.fixture(autouse=True)
+def first_pass(request, monkeypatch):
+    monkeypatch.setenv("GA_LANES", request.module.GA_LANES_FIRST)
+
+
 def test_linear(lib):
     cases.case_wave_primitives_on_hardware(lib)
 

@@ -22,10 +22,7 @@ def lib():
 def _first_pass(request, monkeypatch):
     """both first passes of the emulated ladder: the lanes = reads program, or the wave-per-read program over everything"""
     monkeypatch.delenv("GA_TEST_WAVE_SLOTS", raising=False)
-    if request.param == "lanes-first":
-        monkeypatch.delenv("GA_EMUL_NO_LANES", raising=False)
-    else:
-        monkeypatch.setenv("GA_EMUL_NO_LANES", "1")
+    monkeypatch.setenv("GA_LANES", "1" if request.param == "lanes-first" else "0")
 
 
 @pytest.mark.parametrize("node_len", [64, 1], ids=["64-bp-nodes", "1-bp-nodes"])

@@ -201,6 +201,7 @@ def test_redo_cases_equal_the_oracle(lib, switches, trace):
         assert len(devs) == len(reads)
         for d, o, desc, c in zip(devs, oras, descs, classes):
             pc.compare_read(d, pc.expected(o, trace), "fan %s draw %d %s" % (fan, desc[2], sorted(c["events"])))
+        rc.check_sparse_reads_climbed(devs, oras)
 
 
 @TRACE

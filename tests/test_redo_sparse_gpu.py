@@ -74,7 +74,7 @@ def sparse_variant_took(passes, oras, devs, slots=None):
     need = rc.sparse_parts(oras)
     assert need >= 1
     assert max(p[1] for p in lines) >= need, (lines, need)
-    assert all(d["kernel_pass"] > 0 for d, o in zip(devs, oras) if o["sparse_slices"] > 0), [d["kernel_pass"] for d in devs]
+    rc.check_sparse_reads_climbed(devs, oras)
     if slots is not None:
         assert all(p[2] <= slots for p in passes), passes
         assert any(p[2] == slots and p[1] > slots and p[1] >= need for p in lines), ("no wave took job after job", lines)

@@ -41,10 +41,9 @@ def _passes(capfd):
 def test_parity(name, capfd):
     capfd.readouterr()
     devs, oras = wc.check_case(wc.CASES[name], ctx=name)
-    # the three reads through the fan were finished by the pass this is about, and by a later pass than the first
+    # the three reads through the fan were finished by the pass this is about (and by a later pass than the first: check_case)
     line = cases.passes_of(_passes(capfd), WIDE)[0]
     assert line[1] >= 3, line
-    assert all(d["kernel_pass"] > 0 for d in devs[:3])
 
 
 def test_the_limit(capfd):

@@ -149,10 +149,10 @@ def test_the_limit(lib):
 
 
 # ---- the two ladders agree where the new pass has nothing to do ---------------------------------------------------------------------
-def _same(a, b, ctx):
+def _same(a, b, ctx, columns=True):
     assert len(a) == len(b)
     for i, (x, y) in enumerate(zip(a, b)):
-        for key in ("status", "failed", "score", "query_position", "alignment_start", "alignment_end", "mappings", "columns"):
+        for key in ("status", "failed", "score", "query_position", "alignment_start", "alignment_end", "mappings") + (("columns",) if columns else ()):
             assert x[key] == y[key], (ctx, "read", i, key, x[key], y[key])
         assert x["trace"].shape == y["trace"].shape and (x["trace"] == y["trace"]).all(), (ctx, "read", i, "trace items")
 
@@ -170,11 +170,15 @@ def test_ladders_agree_on_a_wide_bit_vector_case(lib, hooks):
 
 
 def test_ladders_agree_on_the_bit_vector_limit(lib):
+    """here the new pass has something to do: by the product's rule (ga_ladder.h) it takes every job that <256,true,true> left with
+    GA_CAP_NODES, these bit-vector bands of more than 4 096 nodes too, and gives up on them as every pass before it.  What the caller
+    gets is the same -- status 10, failed, no alignment -- except `columns`: a failed read carries the column count of the pass that ran
+    it last, so with the pass withheld it is that of <256,true,true>."""
     with pc.emul_profile("emul_wide"):
         a, _ = wc.check_limit(lib)
     with pc.emul_profile("emul_wide_sparse"):
         b, _ = wc.check_limit(lib)
-    _same(a, b, "wide_cases.LIMIT")
+    _same(a, b, "wide_cases.LIMIT", columns=False)
 
 
 def test_ladders_agree_on_the_pinned_capacity_misses(lib, hooks):

@@ -61,7 +61,6 @@ def test_parity(name, trace, capfd):
     devs, oras = wsc.check_case(name, trace=trace, ctx=name)
     passes, left = _passes(capfd)
     assert _took_what_was_left(passes, left) >= 3
-    assert all(d["kernel_pass"] > 0 for d in devs[:3])
 
 
 def test_the_limit(capfd):

@@ -66,6 +66,8 @@ def check_case(case, lib_path=None, trace=True, ctx=""):
                                  ctx="%s fan %d x %d bw %d/%d%s" % (ctx, branches, branch_len, bw, ramp, " cyclic" if cyclic else ""))
     assert all(o["status"] == 0 and o["sparse_slices"] == 0 for o in oras), [(o["status"], o["sparse_slices"]) for o in oras]
     assert all(d["status"] == 0 for d in devs)
+    # the three reads through the fan were finished by a later pass than the first
+    assert all(d["kernel_pass"] > 0 for d in devs[:3]), [d["kernel_pass"] for d in devs]
     return devs, oras
 
 

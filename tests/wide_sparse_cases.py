@@ -55,6 +55,8 @@ def check_case(name, lib=None, trace=True, ctx=""):
     check_oracle(name, oras)
     assert all(d["status"] != 10 for d in devs), [d["status"] for d in devs]
     assert [d["status"] for d in devs] == [o["status"] for o in oras]
+    # the three reads through the fan were finished by a later pass than the first
+    assert all(d["kernel_pass"] > 0 for d in devs[:3]), [d["kernel_pass"] for d in devs]
     return devs, oras
 
 
