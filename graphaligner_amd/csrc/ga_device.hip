@@ -152,11 +152,13 @@ __global__ void __launch_bounds__(64) ga_wide_sparse_kernel(GaLaunch L)
 // ---- lanes = reads (ga_lanes.h): every lane owns one job, the wave's lanes advance slice by slice together -----------
 // N band nodes per lane in LDS (10 N words per lane), slice records in blocks of R columns per lane, LW = lane stride of
 // the LDS tables = how many lanes of a wave carry jobs.
-template <int N, int LW>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) ga_lanes_kernel(gal::GaLanesLaunch L)
+// FORM: what the traceback hands back, 1 node runs or 0 moves, fixed when the kernel is compiled (lane_finish).  Each size is built
+// twice: ga_lanes_kernel<N, LW> hands back node runs, ga_lanes_moves_kernel<N, LW> moves; the launch picks by GaLanesLaunch::emit_runs.
+template <int N> constexpr int kLanesLdsWords(int lw) { return gal::Lay<N>::WORDS * lw + lw * gal::kStageWords64 * 2 + 128; }  // tables, the staging image of LW lanes, the lanes' arena blocks
+template <int N, int LW, int FORM>
+__device__ __forceinline__ void lanes_wave(const gal::GaLanesLaunch& L, uint32_t* lds)
 {
 	using namespace gal;
-	__shared__ uint32_t lds[Lay<N>::WORDS * LW + LW * kStageWords64 * 2 + 128];  // tables, the staging image of LW lanes, the lanes' arena blocks
 	const int lane = (int)threadIdx.x;
 	const WaveLayout lay = wave_layout<N>(L.cap_cols, L.cap_rows, L.max_slices, L.cap_moves, LW);
 	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.wave_bytes;
@@ -201,7 +203,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
 			lane_end_slice<N>(L, m, st, slice);
 			GAL_LAP(2);
 		}
-		lane_finish<N>(L, m, st, hasJob);
+		lane_finish<N, FORM>(L, m, st, hasJob);
 		GAL_LAP(3);
 #undef GAL_LAP
 #ifdef GA_STAMPS
@@ -224,6 +226,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
 #endif
 		__syncthreads();
 	}
+}
+template <int N, int LW>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) ga_lanes_kernel(gal::GaLanesLaunch L)
+{
+	__shared__ uint32_t lds[kLanesLdsWords<N>(LW)];
+	lanes_wave<N, LW, 1>(L, lds);
+}
+template <int N, int LW>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) ga_lanes_moves_kernel(gal::GaLanesLaunch L)
+{
+	__shared__ uint32_t lds[kLanesLdsWords<N>(LW)];
+	lanes_wave<N, LW, 0>(L, lds);
 }
 
 // ---- the match words of the lanes = reads kernel, built from the reads' bytes (ga_backend.h: GaEqSource) -------------------------
@@ -961,7 +975,8 @@ struct DevBatch : GaBackendBatch
 		{
 			hipMemsetAsync(L.next_job, 0, 16, stream);
 			hipEventRecord(evA, stream);
-			hipLaunchKernelGGL((ga_lanes_kernel<N, LW>), dim3(waves), dim3(64), 0, stream, P);
+			if (P.emit_runs) hipLaunchKernelGGL((ga_lanes_kernel<N, LW>), dim3(waves), dim3(64), 0, stream, P);
+			else hipLaunchKernelGGL((ga_lanes_moves_kernel<N, LW>), dim3(waves), dim3(64), 0, stream, P);
 			float ms = 0;
 			rc = afterPass(ms);
 			if (first) { st.main_ms = ms; st.main_variant = N * 1000 + 80 + (LW == 64 ? 0 : 1); st.slots = waves; st.waves_per_cu = wavesPerCu; st.scratch_bytes = (uint64_t)waves * lay.bytes; }

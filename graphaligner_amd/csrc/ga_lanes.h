@@ -1225,9 +1225,13 @@ GAL_FN bool claim_for_wave(uint64_t* top, uint64_t cap, uint64_t bytes, uint64_t
 #endif
 
 // ---- traceback (getTraceFromTable :894-957 with pickBacktracePredecessor :493-591) and the job's output ----------
-template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& m, LaneState& st, bool hasJob)
+// FORM is what the traceback hands back: 1 node runs, 0 moves, -1 whatever L.emit_runs says at run time (the host emulation).  The
+// kernels are built once per constant form: what only the other form needs is then not in the code at all (`if constexpr` below).
+template <int N, int FORM = -1> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& m, LaneState& st, bool hasJob)
 {
 	typedef Lay<N> LY;
+	static_assert(FORM >= -1 && FORM <= 1, "output form: -1 at run time, 0 moves, 1 node runs");
+	constexpr bool kMayRun = FORM != 0, kMayMove = FORM != 1;      // which forms this instantiation can hand back
 	if (!hasJob) return;
 	const GaDevGraph& g = L.graph;
 	const Lds& l = m.lds;
@@ -1301,16 +1305,19 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 		// node runs instead of moves (L.emit_runs): a run is opened at the first cell met in a node (its last cell on the read) once
 		// the trace is below the rows that do not count, and written out with its first cell when the path leaves the node
 		bool tracing = true;
-		const bool emitRuns = L.emit_runs != 0;
+		const bool emitRuns = FORM < 0 ? L.emit_runs != 0 : FORM != 0;
 		const uint32_t traceRows = st.traceRows;
 		const uint32_t capRunWords = (L.cap_moves + 3) / 4 + 8;
 		uint32_t nRuns = 0, runLastOff = (uint32_t)offset, runLastRow = row;
 		bool started = row < traceRows;
 		auto emitRun = [&](uint32_t n, uint32_t firstOff, uint32_t firstRow) {
-			if (5 * (nRuns + 1) > capRunWords) { status = GA_CAP_TRACE; tracing = false; return; }
-			uint32_t* d = m.moves + (uint64_t)(5 * nRuns) * m.ls;
-			d[0] = n; d[1 * m.ls] = firstOff; d[2 * m.ls] = firstRow; d[3 * m.ls] = runLastOff; d[4 * m.ls] = runLastRow;
-			nRuns++;
+			if constexpr (kMayRun)
+			{
+				if (5 * (nRuns + 1) > capRunWords) { status = GA_CAP_TRACE; tracing = false; return; }
+				uint32_t* d = m.moves + (uint64_t)(5 * nRuns) * m.ls;
+				d[0] = n; d[1 * m.ls] = firstOff; d[2 * m.ls] = firstRow; d[3 * m.ls] = runLastOff; d[4 * m.ls] = runLastRow;
+				nRuns++;
+			}
 		};
 		uint64_t e[4];
 		auto loadEq = [&](uint32_t sl) { const uint64_t* q = st.eq + (uint64_t)sl * 5; e[0] = q[0]; e[1] = q[1]; e[2] = q[2]; e[3] = q[3]; };
@@ -1372,12 +1379,22 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 			c.vn = ((uint64_t)l.rd(at + 3) << 32) | l.rd(at + 2);
 			c.before = (int)l.rd(at + 4);
 		};
+		// the window read of the tight loop: `w` is the word offset of the column's record from the lane's LDS base (lane stride included)
+		auto winReadAt = [&](int w, Col& c) {
+			const uint32_t* p = l.base + w;
+			c.vp = ((uint64_t)p[l.lw] << 32) | p[0];
+			c.vn = ((uint64_t)p[3 * l.lw] << 32) | p[2 * l.lw];
+			c.before = (int)p[4 * l.lw];
+		};
 		auto putMove = [&](int res, int via) {
-			if (emitRuns) return;
-			const uint32_t code = res == 1 ? GA_MOVE_LEFT : res == 2 ? GA_MOVE_DIAG : GA_MOVE_UP;
-			pack |= (code | (res == 3 ? 0u : ((uint32_t)via << 2))) << (8 * (len & 3));
-			if ((len & 3) == 3) { m.moves[(uint64_t)(len >> 2) * m.ls] = pack; pack = 0; }
-			len++;
+			if constexpr (kMayMove)
+			{
+				if (emitRuns) return;
+				const uint32_t code = res == 1 ? GA_MOVE_LEFT : res == 2 ? GA_MOVE_DIAG : GA_MOVE_UP;
+				pack |= (code | (res == 3 ? 0u : ((uint32_t)via << 2))) << (8 * (len & 3));
+				if ((len & 3) == 3) { m.moves[(uint64_t)(len >> 2) * m.ls] = pack; pack = 0; }
+				len++;
+			}
 		};
 		// 32 bases from graph column `col` on, 2 bits each
 		auto bases32 = [&](uint64_t col, uint32_t w0, uint32_t w1, uint32_t w2) -> uint64_t {
@@ -1387,7 +1404,7 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 #ifdef GA_EMULATE
 #define GAL_ANY(x) (x)
 #else
-#define GAL_ANY(x) (__ballot(x) != 0)
+#define GAL_ANY(x) (__builtin_amdgcn_ballot_w64((bool)(x)) != 0)
 #endif
 		bool firstRound = true;                       // the first round sets the lane up (no lane has a window yet)
 		uint64_t lapT = lap_clock();
@@ -1405,12 +1422,33 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 				int here = q0.before + __builtin_popcountll(q0.vp & mR) - __builtin_popcountll(q0.vn & mR);
 				// (straight-line, predicated: a lane that cannot step keeps its state through the selects; the column after next is
 				// requested from the window one step ahead and only looked at when the step has moved a column left)
+				// What does not change during a burst is worked out here, and what the loop carries is carried as plain integers, one register
+				// per lane each (flags carried as `bool`s across this loop were merged lane mask by lane mask at every join):
+				//  spanT  a lane can step while its column is one of the window's columns 1 .. spanT, counted from wLo: the window's last
+				//         column for a lane that traces, 0 for one that does not (any more: a failed assert sets it to 0, and `tracing`
+				//         follows after the loop)
+				//  w2     where the record of column offset - 2 lies in LDS, as a word offset from the lane's base: a step to the left lowers
+				//         it by one record.  A lane on the window's first two columns reads the words below the window there (the node
+				//         tables: inside the lane's LDS, never looked at -- the step after such a read is not a tight one); a lane outside
+				//         the window does not move and keeps reading the window's first record.
+				// Rows only ever go down, a run is open from the first cell below `traceRows` on, and a window reaches into one in-neighbour
+				// only, so a burst crosses into it once at most: `started`, `crossed` and `xStarted` follow from the rows after the loop.
+				const int colStride = 5 * l.lw, w0 = tWIN * l.lw;
+				const int span = wHi - wLo, wLo1 = wLo + 1, rel0 = offset - wLo;
+				uint32_t spanT = (tracing & (span > 0)) ? (uint32_t)span : 0u;
+				int w2 = ((rel0 >= 1) & (rel0 <= span)) ? w0 + (rel0 - 2) * colStride : w0;
+				const bool startedIn = started;
+				const uint32_t beginRow = startedIn ? 0xfffffffeu : traceRows - 1;    // the row whose first cell opens the first run (no row: it is open)
+				(void)beginRow;
 				Col q2;
-				winRead(((offset >= wLo + 2) & (offset <= wHi)) ? offset - 2 : wLo, q2);
-				for (int it = 0; it < kBurst; it++)
+				winReadAt(w2, q2);
+				// (both ways out of the loop are taken at its head, on one scalar condition)
+				for (int it = 0; ; it++)
 				{
-					const bool fast = tracing & (r > 0) & (offset > wLo) & (offset <= wHi) & (len + 8 < capMoves);       // (& not &&: no branches)
-					if (!GAL_ANY(fast)) break;
+					const uint32_t u = (uint32_t)(offset - wLo1);                      // the column, counted from the window's second one
+					bool fast = (r > 0) & (u < spanT);                                 // (& not &&: no branches)
+					if constexpr (kMayMove) fast = fast & (len + 8 < capMoves);       // (node runs never fill the plane from here: emitRun checks)
+					if ((it >= kBurst) | !GAL_ANY(fast)) break;
 #ifdef GA_STAMPS
 					st.laps[7] += 1ull << 32;
 #endif
@@ -1420,7 +1458,7 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 					const int horizontal = q1.before + __builtin_popcountll(q1.vp & mR) - __builtin_popcountll(q1.vn & mR);
 					const int diagonal = horizontal - (int)((uint32_t)(q1.vp >> sr) & 1u) + (int)((uint32_t)(q1.vn >> sr) & 1u);
 					const int up = here - (int)((uint32_t)(q0.vp >> sr) & 1u) + (int)((uint32_t)(q0.vn >> sr) & 1u);
-					const int base = (int)(wbases >> (2 * ((offset - wLo) & 31))) & 3;
+					const int base = (int)(wbases >> ((2 * u + 2) & 62)) & 3;
 					const int want = here - 1 + (int)((e[base] >> sr) & 1);            // the diagonal cell's score if the step is diagonal
 					const bool left = horizontal == here - 1;
 					const bool diag = !left & (diagonal == want);
@@ -1431,30 +1469,47 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 #ifdef GA_DEBUG_SITE
 					site = fast & bad ? ((horizontal < here - 1) ? 1 : (!left & (diagonal < want)) ? 2 : 3) : site;
 #endif
-					tracing = tracing & !(fast & bad);
+					spanT = (fast & bad) ? 0u : spanT;
 					const bool colMove = ok & (left | diag), rowMove = ok & !left;
-					const bool crossNow = colMove & (offset == 0);                      // into the in-neighbour (only a window that reaches below 0 gets here)
-					xRowBefore = crossNow ? row : xRowBefore;
-					xStarted = crossNow ? started : xStarted;
-					crossed = crossed | crossNow;
+					bool crossNow = false;                                              // into the in-neighbour (only a window that reaches below 0 gets here)
+					if constexpr (kMayRun) { crossNow = colMove & (offset == 0); xRowBefore = crossNow ? row : xRowBefore; }
 					here = ok ? (left ? horizontal : diag ? diagonal : up) : here;
 					row -= rowMove ? 1u : 0u;
 					r -= rowMove ? 1 : 0;
 					mR = rowMove ? mR >> 1 : mR;
-					xRowAfter = crossNow ? row : xRowAfter;
+					if constexpr (kMayRun) xRowAfter = crossNow ? row : xRowAfter;
 					offset -= colMove ? 1 : 0;
+					w2 -= colMove ? colStride : 0;
 					q0.vp = colMove ? q1.vp : q0.vp; q0.vn = colMove ? q1.vn : q0.vn; q0.before = colMove ? q1.before : q0.before;
 					q1.vp = colMove ? q2.vp : q1.vp; q1.vn = colMove ? q2.vn : q1.vn; q1.before = colMove ? q2.before : q1.before;
-					winRead(((offset >= wLo + 2) & (offset <= wHi)) ? offset - 2 : wLo, q2);
-					if (emitRuns)
+					winReadAt(w2, q2);
+					if constexpr (kMayRun)
 					{
-						// (the first cell below the rows that do not count opens the first run)
-						const bool begin = ok & !started & (row < traceRows);
+						// (the first cell below the rows that do not count opens the first run: the row went down to `beginRow` in this step)
+						const bool begin = rowMove & (row == beginRow);
 						runLastOff = begin ? (uint32_t)offset : runLastOff;
 						runLastRow = begin ? row : runLastRow;
-						started = started | begin;
 					}
-					else if (ok) putMove(left ? 1 : diag ? 2 : 3, 0);
+					if constexpr (kMayMove)
+					{
+						if (!emitRuns)
+						{
+							// (putMove with no neighbour index, predicated like the rest of the step: a word of four moves goes out when it is full)
+							const uint32_t code = left ? GA_MOVE_LEFT : diag ? GA_MOVE_DIAG : GA_MOVE_UP;
+							pack |= ok ? code << (8 * (len & 3)) : 0u;
+							const bool full = ok & ((len & 3) == 3);
+							if (full) m.moves[(uint64_t)(len >> 2) * m.ls] = pack;
+							pack = full ? 0u : pack;
+							len += ok ? 1u : 0u;
+						}
+					}
+				}
+				tracing = tracing & (status == GA_OK);                                  // (a status other than GA_OK always ends the lane)
+				crossed = offset < 0;                                                   // (a lane comes here with offset >= 0: the round before saw to that)
+				if constexpr (kMayRun)
+				{
+					xStarted = startedIn | (xRowBefore < traceRows);                     // (looked at when crossed: the run was open in the cell the lane left)
+					started = startedIn | (row < traceRows);
 				}
 			}
 			{ const uint64_t t2 = lap_clock(); st.laps[0] += t2 - lapT; lapT = t2; }
@@ -1473,7 +1528,7 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 			{
 				const uint64_t g0 = lap_clock();
 				if (row == 0xffffffffu) { tracing = false; continue; }               // reached the row before the first one
-				if (len + 8 >= capMoves) { status = GA_CAP_TRACE; tracing = false; continue; }
+				if constexpr (kMayMove) { if (len + 8 >= capMoves) { status = GA_CAP_TRACE; tracing = false; continue; } }
 				if (roundsLeft-- == 0) { status = GA_PUNT; tracing = false; continue; }          // (every round moves its lane; the bound is what ends the loop should one ever not)
 				const uint32_t safeRow = 0;
 				// a tight step took the lane into the in-neighbour: its coordinates follow (what the decision below does for a step it takes itself)
@@ -1491,11 +1546,15 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 					// (the run of the node left is written AFTER the lane's state has moved, and a run that does not fit ends the lane below:
 					// with `if (!tracing) continue;` between the two, hipcc 7.2 kept the OLD nb[] / nbLen[] for every lane that had a run to
 					// write -- profiles/r3_miscompile_normalization_isa.txt)
-					if (emitRuns)
+					if constexpr (kMayRun)
 					{
-						if (xStarted) { emitRun(oldNode, 0, xRowBefore); runLastOff = L0 - 1; runLastRow = xRowAfter; }
-						else if (started) runLastOff += L0;                              // (the run was opened in the new node, at a column counted from the old one)
+						if (emitRuns)
+						{
+							if (xStarted) { emitRun(oldNode, 0, xRowBefore); runLastOff = L0 - 1; runLastRow = xRowAfter; }
+							else if (started) runLastOff += L0;                          // (the run was opened in the new node, at a column counted from the old one)
+						}
 					}
+					(void)oldNode;
 				}
 				if (!tracing) continue;
 				if (inDeg > 4) { status = GA_PUNT; tracing = false; continue; }
@@ -1584,10 +1643,10 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 					if (offset > wLo) winRead(offset - 1, q1);
 				}
 				const int here = col_value(q0.vp, q0.vn, q0.before, r);
-				if (emitRuns && !started && row < traceRows) { started = true; runLastOff = (uint32_t)offset; runLastRow = row; }
+				if constexpr (kMayRun) { if (emitRuns && !started && row < traceRows) { started = true; runLastOff = (uint32_t)offset; runLastRow = row; } }
 				if (row == 0 && node == st.seedNode && (here == 0 || here == 1))                                                      // free start (:500)
 				{
-					if (emitRuns && started) emitRun(node, (uint32_t)offset, row);
+					if constexpr (kMayRun) { if (emitRuns && started) emitRun(node, (uint32_t)offset, row); }
 					row = 0xffffffffu; tracing = false; continue;
 				}
 				const uint32_t rowBefore = row;
@@ -1658,11 +1717,11 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 				// put the move away (the step onto the row before the first one is not part of the trace, :949-950)
 				if (row == 0xffffffffu)
 				{
-					if (emitRuns && started) emitRun(curNode, curOffset, rowBefore);     // the trace ends in the cell the step left
+					if constexpr (kMayRun) { if (emitRuns && started) emitRun(curNode, curOffset, rowBefore); }     // the trace ends in the cell the step left
 					tracing = false; continue;
 				}
 				putMove(res, via);
-				if (emitRuns)
+				if constexpr (kMayRun) if (emitRuns)
 				{
 					if (curOffset == 0 && res != 3 && node != curNode)
 					{
@@ -1810,12 +1869,15 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 		if (status != GA_OK) out.stamps[site & 7] = 1;
 #endif
 		{ const uint64_t t2 = lap_clock(); st.laps[1] += t2 - lapT; lapT = t2; }
-		if (!emitRuns && (len & 3)) m.moves[(uint64_t)(len >> 2) * m.ls] = pack;
+		if constexpr (kMayMove) { if (!emitRuns && (len & 3)) m.moves[(uint64_t)(len >> 2) * m.ls] = pack; }
 		st.laps[3] = lap_clock();
 		// hand the moves (or runs) over: claim their bytes (rounded to words) of the pool and copy them
 		if (status == GA_OK)
 		{
-			const uint32_t words = emitRuns ? 5 * nRuns : (len + 3) / 4;
+			uint32_t words = 0;
+			if constexpr (FORM == 1) words = 5 * nRuns;
+			else if constexpr (FORM == 0) words = (len + 3) / 4;
+			else words = emitRuns ? 5 * nRuns : (len + 3) / 4;
 			// the claim only ever commits when it fits (compare-and-swap): an overshoot that is rolled back later could leave the pool's
 			// top below a region another lane claimed in between.  The lanes of a wave get here together: one of them claims for all
 			// (a compare-and-swap per lane on one address is tens of thousands of lanes retrying against each other), and only a wave
@@ -1840,8 +1902,9 @@ template <int N> GAL_FN void lane_finish(const GaLanesLaunch& L, const LaneMem& 
 					for (int i = 0; i < 8; i++) if (k + (uint32_t)i < words) dst[k + (uint32_t)i] = a[i];
 				}
 				out.trace_off = at;
-				out.trace_len = emitRuns ? nRuns : len;
-				out.reserved3 = emitRuns ? 1u : 0u;
+				if constexpr (FORM == 1) { out.trace_len = nRuns; out.reserved3 = 1u; }
+				else if constexpr (FORM == 0) { out.trace_len = len; out.reserved3 = 0u; }
+				else { out.trace_len = emitRuns ? nRuns : len; out.reserved3 = emitRuns ? 1u : 0u; }
 				out.n_node_steps = nodeSteps;
 			}
 		}

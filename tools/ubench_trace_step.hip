@@ -1,6 +1,10 @@
 // ubench_trace_step.hip -- what one fast traceback step of the lanes = reads kernel costs a lone wave (one wave per SIMD, 782 waves,
 // every lane walking a diagonal through a synthetic window in LDS), with parts of the step switched off one at a time.
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench_trace_step.hip -o tools/ubench_trace_step && tools/ubench_trace_step
+// This models ROUND 2's step: moves stored from inside the step, the window address multiplied out from the column, no crossing into
+// the in-neighbour and no node runs.  The shipped step (csrc/ga_lanes.h, lane_finish<N, FORM>) is built per output form, keeps a
+// running window address and stores nothing in the node-run form; what the compiler makes of it is counted by tools/loop_census.py
+// (profiles/trace_step_census.txt: 110 instructions per step for node runs), not by this file.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
