@@ -1,5 +1,5 @@
 // ga_backend.h -- the seam between the host library (graph model, job building, result
-// assembly: ga_host.cpp) and whatever executes the extension program.  The product links
+// assembly: ga_host.cpp with its parts ga_prepare.h and ga_collect.h) and whatever executes the extension program.  The product links
 // ga_device.hip (gfx950, HIP).  tests/emul/ links a host emulation of the same programs so the
 // device logic can be checked in the CPU-only container; that object is never part of the
 // shipped library.  (It can withhold a capability, tests/emul/ga_emul.h: it then answers with the defaults of the classes below.)
