@@ -526,6 +526,28 @@ class Pileup:
             pass
 
 
+def fold_edge_support(edge_list, counts):
+    """per bidirected edge the summed counts of its two directed edges.  edge_list: the arrays (from_id, to_id) of digraph ids
+    (2 * bigraph id + strand) of directed edges; counts: one per edge.  The directed edge a -> b and its mirror b ^ 1 -> a ^ 1 are the two
+    strands' copies of one edge of the bigraph and fall under one key, the smaller of the two pairs; an edge listed twice is summed too.
+    Returns a dict (from_id, to_id) -> count.  With counts of the alignments that cross each directed edge, an edge of the bigraph is
+    supported when its folded count is >= 1"""
+    from_id, to_id = (np.asarray(x, dtype=np.int64).reshape(-1) for x in edge_list)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if not (len(from_id) == len(to_id) == len(counts)):
+        raise ValueError("fold_edge_support: one count per directed edge")
+    if not len(counts):
+        return {}
+    # the smaller of (a, b) and (b ^ 1, a ^ 1), compared as pairs; then one sum per distinct key
+    ma, mb = to_id ^ 1, from_id ^ 1
+    own = (from_id < ma) | ((from_id == ma) & (to_id <= mb))
+    keys = np.stack([np.where(own, from_id, ma), np.where(own, to_id, mb)], axis=1)
+    uniq, inverse = np.unique(keys, axis=0, return_inverse=True)
+    sums = np.zeros(len(uniq), dtype=np.int64)
+    np.add.at(sums, inverse.reshape(-1), counts)
+    return {(int(a), int(b)): int(c) for (a, b), c in zip(uniq.tolist(), sums.tolist())}
+
+
 class Batch:
     def __init__(self, graph, reads, seeds, bw, ramp, flags, names=None, find_seeds=None):
         self.g = graph
