@@ -149,6 +149,7 @@ class AlignerParams:
         self.seedCoord = "file"     # --seed-coord: "file" or "topology"
         self.opsFile = ""           # --ops-out: per aligned read its operations (GA_F_OPS): counts, identity and the run string
         self.pileupFile = ""        # --pileup-out: per graph base that any aligned read touches, the eight counts of a pileup (GA_F_PILEUP)
+        self.edgeSupportFile = ""   # --edge-support-out: per edge of the bigraph that any aligned read crosses, its count (a pileup of kind "edges")
 
 
 def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr):
@@ -161,7 +162,8 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
     # (GA_F_OPS only when its file is asked for: the other output is the same with and without it)
     flags = binding.GA_F_TRACE | (binding.GA_F_OPS if getattr(params, "opsFile", "") else 0)
     want_pileup = bool(getattr(params, "pileupFile", ""))
-    if want_pileup:
+    want_edges = bool(getattr(params, "edgeSupportFile", ""))
+    if want_pileup or want_edges:
         flags |= binding.GA_F_PILEUP
     find_seeds = getattr(params, "findSeeds", False)
     if params.seedFile == "" and not find_seeds:
@@ -214,14 +216,16 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
     with_seeds = [i for i in order if i in seeds_of]
     results = {}
     pile = graph.pileup("bases") if want_pileup else None
+    edge_pile = graph.pileup("edges") if want_edges else None
+    piles = [p for p in (pile, edge_pile) if p is not None]       # (one flagged batch is added to each in turn)
     if find_seeds and seeded is not None:
         try:
             seeded.run()
             for i, r in zip(order, seeded.collect()):
                 if i in seeds_of:
                     results[i] = r
-            if pile is not None:
-                pile.add(seeded)
+            for p in piles:
+                p.add(seeded)
         finally:
             seeded.close()
     elif with_seeds:
@@ -230,8 +234,8 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
         batch.run()
         for i, r in zip(with_seeds, batch.collect()):
             results[i] = r
-        if pile is not None:
-            pile.add(batch)
+        for p in piles:
+            p.add(batch)
     written = []
     left = len(reads)
     for i in order:
@@ -291,7 +295,24 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
                                                              c["match"] / cells if cells else 0.0, binding.ops_string(r["ops"])))
     if pile is not None:
         write_pileup(params.pileupFile, pile, [r for r in results.values() if r["status"] == 0 and not r["failed"]])
+    if edge_pile is not None:
+        write_edge_support(params.edgeSupportFile, edge_pile)
     return [(rd.seq_id, r) for rd, r in written]
+
+
+def write_edge_support(path, pile):
+    """one line per edge of the bigraph whose folded count (the directed edge and its mirror summed) is >= 1: from_id from_reverse to_id
+    to_reverse count, ordered by those.  The written counts must add up to what the pileup says it was given"""
+    folded = pile.edge_support()
+    written = 0
+    with open(path, "w") as f:
+        for (a, b), c in sorted(folded.items()):
+            if c >= 1:
+                written += c
+                f.write("%d %d %d %d %d\n" % (a >> 1, a & 1, b >> 1, b & 1, c))
+    total = int(pile.stats()["items_added"])
+    if written != total:
+        raise RuntimeError("edge support: %d counts written, %d items added to the pileup" % (written, total))
 
 
 def write_pileup(path, pile, aligned):
@@ -325,7 +346,7 @@ def parse_args(argv, err=sys.stderr):
     p = AlignerParams()
     initial_full_band = False
     coord_given = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out=", "pileup-out="])
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out=", "pileup-out=", "edge-support-out="])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -364,6 +385,8 @@ def parse_args(argv, err=sys.stderr):
             p.opsFile = a
         elif o == "--pileup-out":
             p.pileupFile = a
+        elif o == "--edge-support-out":
+            p.edgeSupportFile = a
 
     def stop(msg):
         err.write(msg + "\n")

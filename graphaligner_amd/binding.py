@@ -19,6 +19,10 @@ GA_F_OPS = 2
 GA_F_PILEUP = 4
 GA_PILEUP_DEPTH = 1
 GA_PILEUP_BASES = 8
+GA_PILEUP_EDGES = 32
+# kind, planes and entries are three things (include/graphaligner_amd.h, "pileups"): the counters one entry has, per kind
+PILEUP_KINDS = {"bases": GA_PILEUP_BASES, "depth": GA_PILEUP_DEPTH, "edges": GA_PILEUP_EDGES}
+PILEUP_PLANES_OF_KIND = {GA_PILEUP_BASES: 8, GA_PILEUP_DEPTH: 1, GA_PILEUP_EDGES: 1}
 PILEUP_PLANES = ("match", "mismatch_A", "mismatch_C", "mismatch_G", "mismatch_T", "mismatch_other", "deletion", "insertion")
 OP_CODES = {1: "=", 2: "X", 3: "I", 4: "D", 5: "|"}
 GA_S_OK = 0
@@ -192,6 +196,9 @@ def load(path=None):
         L.ga_batch_pileup_add.argtypes = [C.c_void_p, C.c_void_p]
         L.ga_pileup_download.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.ga_pileup_stats.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "ga_graph_edge_slots"):                                  # (bench.py --lib may name a build from before edge support)
+        L.ga_graph_edge_slot_count.argtypes = [C.c_void_p, C.c_void_p]
+        L.ga_graph_edge_slots.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     if hasattr(L, "ga_find_seeds"):
         L.ga_seed_params_default.argtypes = [C.c_void_p]
         L.ga_seed_params_default.restype = None
@@ -274,9 +281,25 @@ class Graph:
 
     # ---- pileups (include/graphaligner_amd.h: "pileups") ----
     def pileup(self, kind="bases"):
-        """counters per column of this graph that stay on the device: kind "bases" (8 planes, binding.PILEUP_PLANES) or "depth" (1 plane).
-        Batches prepared with GA_F_PILEUP add to it after their collect (Pileup.add)"""
+        """counters of this graph that stay on the device: kind "bases" (8 planes per column, binding.PILEUP_PLANES), "depth" (1 plane per
+        column) or "edges" (1 plane per slot of edge_slots(): the alignments that cross each directed edge).  Batches prepared with
+        GA_F_PILEUP add to it after their collect (Pileup.add)"""
         return Pileup(self, kind)
+
+    def edge_slot_count(self):
+        if not hasattr(self.L, "ga_graph_edge_slots"):
+            raise RuntimeError("this library has no edge slots")
+        n = C.c_uint64()
+        _check(self.L, self.L.ga_graph_edge_slot_count(self.h, C.byref(n)), "ga_graph_edge_slot_count")
+        return int(n.value)
+
+    def edge_slots(self, first=0, n=None):
+        """(from_ids, to_ids): the digraph ids (2 * bigraph id + strand) of the directed edge of every slot -- the in-neighbour lists of
+        the graph laid end to end in node-index order --, or of n slots from `first`.  Needs no device"""
+        n = self.edge_slot_count() - int(first) if n is None else int(n)
+        from_ids, to_ids = np.zeros(max(n, 0), dtype=np.int64), np.zeros(max(n, 0), dtype=np.int64)
+        _check(self.L, self.L.ga_graph_edge_slots(self.h, int(first), n, from_ids.ctypes.data_as(C.c_void_p), to_ids.ctypes.data_as(C.c_void_p)), "ga_graph_edge_slots")
+        return from_ids, to_ids
 
     def node_columns(self, digraph_id):
         """(first column, length) of the digraph node 2 * bigraph id + strand"""
@@ -473,22 +496,25 @@ class ReadSet:
 
 
 class Pileup:
-    """ga_pileup_t: kind planes of uint32 counters, one entry per column of the graph, in the HBM of the graph's device"""
+    """ga_pileup_t: `planes` planes of uint32 counters over `entries` entries -- the graph's columns, or its edge slots for the kind
+    "edges" --, in the HBM of the graph's device.  `kind_id` is the library's constant of the kind: a name, not a size"""
 
     def __init__(self, graph, kind="bases"):
-        kinds = {"bases": GA_PILEUP_BASES, "depth": GA_PILEUP_DEPTH}
-        if kind not in kinds:
-            raise ValueError("pileup kind must be 'bases' or 'depth'")
+        if kind not in PILEUP_KINDS:
+            raise ValueError("pileup kind must be 'bases', 'depth' or 'edges'")
         self.g = graph                     # (a pileup is freed before its graph: the reference keeps the graph alive)
         self.L = graph.L
         if not hasattr(self.L, "ga_pileup_create"):
             raise RuntimeError("this library has no pileups")
         self.kind = kind
-        self.planes = kinds[kind]
-        self.columns = int(graph.bp)
+        self.kind_id = PILEUP_KINDS[kind]
+        self.planes = PILEUP_PLANES_OF_KIND[self.kind_id]
         h = C.c_void_p()
-        _check(self.L, self.L.ga_pileup_create(graph.h, self.planes, C.byref(h)), "ga_pileup_create")
+        _check(self.L, self.L.ga_pileup_create(graph.h, self.kind_id, C.byref(h)), "ga_pileup_create")
         self.h = h
+        # the entry count is the library's (ga_pileup_stats_t.columns): every buffer handed to a download is sized by it
+        self.entries = int(self.stats()["columns"])
+        self.columns = self.entries
 
     def add(self, batch):
         """adds the alignments of the batch's last collect (a batch prepared with GA_F_PILEUP, collected since its last run)"""
@@ -498,14 +524,25 @@ class Pileup:
         _check(self.L, self.L.ga_pileup_reset(self.h), "ga_pileup_reset")
 
     def counts(self, first_column=0, n_columns=None):
-        """(planes, columns) uint32 array of the whole pileup, or of n_columns columns from first_column"""
-        n = self.columns - first_column if n_columns is None else int(n_columns)
-        out = np.zeros((self.planes, max(n, 0)), dtype=np.uint32)
+        """(planes, entries) uint32 array of the whole pileup, or of n_columns entries (columns; slots for "edges") from first_column"""
+        n = self.entries - int(first_column) if n_columns is None else int(n_columns)
+        if first_column < 0 or n < 0 or int(first_column) + n > self.entries:
+            raise RuntimeError("ga_pileup_download failed: range outside the pileup's %d entries (100)" % self.entries)
+        out = np.zeros((self.planes, n), dtype=np.uint32)
         _check(self.L, self.L.ga_pileup_download(self.h, int(first_column), n, out.ctypes.data_as(C.c_void_p)), "ga_pileup_download")
         return out
 
+    def edge_support(self):
+        """kind "edges": dict (from_id, to_id) -> count per edge of the bigraph, an edge's two directed copies summed (fold_edge_support
+        of Graph.edge_slots() and counts())"""
+        if self.kind != "edges":
+            raise ValueError("edge_support: not a pileup of kind 'edges'")
+        return fold_edge_support(self.g.edge_slots(), self.counts()[0])
+
     def node(self, node_id, reverse=False):
         """(planes, length) array of the node's columns, offset 0 first"""
+        if self.kind == "edges":
+            raise ValueError("node: a pileup of kind 'edges' has slots, not columns")
         first, length = self.g.node_columns(2 * int(node_id) + (1 if reverse else 0))
         return self.counts(first, length)
 

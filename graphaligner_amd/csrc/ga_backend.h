@@ -90,7 +90,8 @@ struct GaOpsOut { const uint32_t* runs = nullptr; const uint64_t* offsets = null
 // what one add is given: the winning jobs (job index | 0x80000000 when the part has cells), longest first, and the items the host derived
 // from TraceItem lists as (plane of the BASES kind << 56 | column)
 constexpr uint32_t GA_PILEUP_COUNTS = 0x80000000u;   // in a list entry: this part of the read's alignment has cells
-struct GaPileupAdd { const uint32_t* list = nullptr; size_t nList = 0; const uint64_t* pairs = nullptr; size_t nPairs = 0; };
+// ... and, for a pileup of the EDGES kind, the crossings of those same lists as slot indices
+struct GaPileupAdd { const uint32_t* list = nullptr; size_t nList = 0; const uint64_t* pairs = nullptr; size_t nPairs = 0; const uint32_t* slots = nullptr; size_t nSlots = 0; };
 // ... and hands back: the HIP-event time of its kernel(s), the jobs walked, the moves read, the items added (both sources)
 struct GaPileupAddOut { double kernel_ms = 0; uint64_t jobs = 0, moves = 0, items = 0; };
 #if defined(__HIPCC__)
@@ -105,12 +106,48 @@ GA_HOST_DEVICE inline uint32_t ga_pileup_plane_in_kind(uint32_t kind, uint32_t b
 	if (kind == 8) return basesPlane < 8 ? basesPlane : 0xffffffffu;
 	return basesPlane < 7 ? 0u : 0xffffffffu;
 }
+// A pileup's sizes in one place.  Its KIND names what is counted (the constants of include/graphaligner_amd.h), its PLANES are how many
+// counters an entry has, its ENTRIES are what is counted over: the graph's columns or, for the EDGES kind, its slots -- the in-neighbour
+// lists laid end to end, ga_edge_slot_count.  Everything that sizes, bounds or copies a pileup goes through these two functions.
+constexpr int GA_KIND_DEPTH = 1, GA_KIND_BASES = 8, GA_KIND_EDGES = 32;
+GA_HOST_DEVICE inline uint32_t ga_pileup_planes_of_kind(int kind) { return kind == GA_KIND_BASES ? 8u : kind == GA_KIND_DEPTH || kind == GA_KIND_EDGES ? 1u : 0u; }
+GA_HOST_DEVICE inline uint64_t ga_pileup_entries(int kind, uint64_t columns, uint64_t slots) { return kind == GA_KIND_EDGES ? slots : columns; }
+// what a back end makes a pileup from; mirrorSlot (EDGES only): per slot the slot of the other strand's copy of the edge, or 0xffffffff
+struct GaPileupSpec { int kind = 0; uint32_t planes = 0; uint64_t entries = 0; const uint32_t* mirrorSlot = nullptr; };
+
+// ---- slots (ga_edges.h): the edge from -> to has the slot in_off[to] + (place of `from` in to's in-list) --------------------------
+inline uint64_t ga_edge_slot_count(const GaFlatGraph& f) { return f.in_off.empty() ? 0 : f.in_off.back(); }
+// 0xffffffff: no such node or no such edge
+inline uint32_t ga_edge_slot_of(const GaFlatGraph& f, uint32_t from, uint32_t to)
+{
+	if (f.in_off.empty() || to >= f.in_off.size() - 1) return 0xffffffffu;       // (no `to + 1`: 0xffffffff, "none", must not wrap)
+	for (uint32_t e = f.in_off[to]; e < f.in_off[to + 1]; e++) if (f.in_nbr[e] == from) return e;
+	return 0xffffffffu;
+}
+// per slot of from -> to the slot of twin(to) -> twin(from); 0xffffffff where a twin or that edge does not exist, or a dummy node is touched
+inline std::vector<uint32_t> ga_edge_mirror_slots(const GaFlatGraph& f, const std::vector<uint32_t>& twin)
+{
+	const uint32_t n = f.in_off.empty() ? 0 : (uint32_t)f.in_off.size() - 1;
+	std::vector<uint32_t> mirror((size_t)ga_edge_slot_count(f), 0xffffffffu);
+	for (uint32_t to = 1; to + 1 < n; to++)
+		for (uint32_t e = f.in_off[to]; e < f.in_off[to + 1]; e++)
+		{
+			const uint32_t from = f.in_nbr[e];
+			if (from == 0 || from >= n - 1 || to >= twin.size() || from >= twin.size()) continue;
+			// (a node whose other strand was never added has the twin 0xffffffff: compared without an add that would wrap)
+			const uint32_t mTo = twin[from], mFrom = twin[to];
+			if (mTo == 0 || mFrom == 0 || mTo >= n - 1 || mFrom >= n - 1) continue;
+			mirror[e] = ga_edge_slot_of(f, mFrom, mTo);
+		}
+	return mirror;
+}
+
 class GaBackendPileup
 {
 public:
 	virtual ~GaBackendPileup() {}
 	virtual int reset() = 0;
-	// out[plane * n + i] = the counter of (plane, first + i)
+	// out[plane * n + i] = the counter of (plane, first + i), for every plane of the kind; first + n <= entries
 	virtual int download(uint64_t first, uint64_t n, uint32_t* out) const = 0;
 };
 
@@ -202,9 +239,9 @@ public:
 	virtual bool buildsMatchWords() const { return false; }
 	// true: this back end codes operations (GaRunConfig::emit_ops); on one that does not, a prepare with GA_F_OPS is refused
 	virtual bool codesOps() const { return false; }
-	// kind planes of zeroed counters per column of this graph, or nullptr + *status (102 = GA_E_DEVICE: no memory).  A back end without
+	// spec.planes planes of spec.entries zeroed counters each, or nullptr + *status (102 = GA_E_DEVICE: no memory).  A back end without
 	// pileups has no factory (100 = GA_E_INVALID) and a prepare with GA_F_PILEUP is refused on it
-	virtual GaBackendPileup* createPileup(int, int* status) { *status = 100; return nullptr; }
+	virtual GaBackendPileup* createPileup(const GaPileupSpec&, int* status) { *status = 100; return nullptr; }
 	virtual bool codesPileup() const { return false; }
 	// host memory for a batch's copy of the reads (the product: pinned blocks from a pool, so that their upload is one DMA transfer)
 	virtual std::shared_ptr<char> hostBlock(size_t bytes)

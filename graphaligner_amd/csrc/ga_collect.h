@@ -235,6 +235,24 @@ void hostPairs(const ga_graph& g, const Trace& bw, const Trace& fw, const std::v
 	}
 }
 
+// the crossings of a read's list as edge slots (the rule of the EDGES kind): two consecutive items of one part -- the cells part[i],
+// part[i + 1], i >= 1 -- in two columns, the second not the next offset of the same node, neither on a dummy node, over an edge of the graph
+void hostSlots(const ga_graph& g, const Trace& bw, const Trace& fw, std::vector<uint32_t>& into)
+{
+	into.clear();
+	const uint32_t lastNode = g.nodeCount() - 1;
+	for (const Trace* part : {&bw, &fw})
+		for (size_t i = 1; i + 1 < part->size(); i++)
+		{
+			const Pos& a = (*part)[i];
+			const Pos& b = (*part)[i + 1];
+			if (a.node == b.node && (b.offset == a.offset || b.offset == a.offset + 1)) continue;
+			if (a.node == 0 || a.node == lastNode || b.node == 0 || b.node == lastNode) continue;
+			const uint32_t slot = ga_edge_slot_of(g.flat, a.node, b.node);
+			if (slot != 0xffffffffu) into.push_back(slot);
+		}
+}
+
 // a TraceItem list's types cut into maximal runs
 void itemRuns(const std::vector<ga_trace_item_t>& items, std::vector<uint32_t>& into)
 {
@@ -255,6 +273,7 @@ struct alignas(64) Scratch
 	std::vector<ga_trace_item_t> items;
 	std::vector<uint32_t> opRuns, pileJobs;
 	std::vector<uint64_t> pilePairs, pairsOfRead;
+	std::vector<uint32_t> pileSlots, slotsOfRead;
 	std::vector<NodeRun> runs;
 	uint64_t columnUpdates = 0;
 };
@@ -335,7 +354,7 @@ int Collector::fetch()
 	if (int s = b->dev->fetch(outs, &moves, &nMoveBytes)) return s;
 	fetched.dev = b->dev;
 	b->collected = false;
-	b->pileList.clear(); b->pilePairs.clear();
+	b->pileList.clear(); b->pilePairs.clear(); b->pileSlots.clear();
 	if (wantOps)
 	{
 		if (int s = b->dev->fetchOps(devOps)) return s;
@@ -638,7 +657,7 @@ bool Collector::derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOp
 	if (!(wantTrace || suspicious || hostOps || hostPile)) return true;
 	const bool fine = traceItems(g, seq, best.bw, best.fw, s.items);
 	if (hostOps) opsFromHost++;
-	if (hostPile && fine) hostPairs(g, best.bw, best.fw, s.items, s.pairsOfRead);
+	if (hostPile && fine) { hostPairs(g, best.bw, best.fw, s.items, s.pairsOfRead); hostSlots(g, best.bw, best.fw, s.slotsOfRead); }
 	if (hostOps && fine) itemRuns(s.items, s.opRuns);
 	if (!wantTrace || !fine) s.items.clear();
 	return fine;
@@ -662,7 +681,12 @@ void Collector::store(size_t ri, ga_read_result_t& rr, const BestSeed& best, Scr
 	}
 	if (wantPile)
 	{
-		if (hostPile) { s.pilePairs.insert(s.pilePairs.end(), s.pairsOfRead.begin(), s.pairsOfRead.end()); pileFromHost++; }
+		if (hostPile)
+		{
+			s.pilePairs.insert(s.pilePairs.end(), s.pairsOfRead.begin(), s.pairsOfRead.end());
+			s.pileSlots.insert(s.pileSlots.end(), s.slotsOfRead.begin(), s.slotsOfRead.end());
+			pileFromHost++;
+		}
 		else
 		{
 			if (!best.bw.empty() && best.bwJob >= 0) s.pileJobs.push_back((uint32_t)best.bwJob | GA_PILEUP_COUNTS);
@@ -722,6 +746,7 @@ void Collector::assemble()
 		b->columnUpdates += scratch[t].columnUpdates;
 		b->pileList.insert(b->pileList.end(), scratch[t].pileJobs.begin(), scratch[t].pileJobs.end());
 		b->pilePairs.insert(b->pilePairs.end(), scratch[t].pilePairs.begin(), scratch[t].pilePairs.end());
+		b->pileSlots.insert(b->pileSlots.end(), scratch[t].pileSlots.begin(), scratch[t].pileSlots.end());
 	}
 	b->opsFromDevice = opsFromDevice.load(); b->opsFromHost = opsFromHost.load();
 	fetched.done();
@@ -731,7 +756,7 @@ void Collector::assemble()
 // ---- stage 4: hand-over ---------------------------------------------------------------------------
 int Collector::publish(ga_results_t** out)
 {
-	if (overflow.load()) { b->pileList.clear(); b->pilePairs.clear(); return GA_E_DEVICE; }
+	if (overflow.load()) { b->pileList.clear(); b->pilePairs.clear(); b->pileSlots.clear(); return GA_E_DEVICE; }
 	if (wantPile)
 	{
 		// longest first, as the passes' own lists are: the kernel deals the entries over its waves statically

@@ -22,6 +22,7 @@
 #include "ga_plan.h"
 #include "ga_ops.h"
 #include "ga_pileup.h"
+#include "ga_edges.h"
 
 namespace {
 
@@ -343,6 +344,18 @@ __global__ void __launch_bounds__(256) ga_pileup_pairs_kernel(const uint64_t* pa
 	if (i < n) gapl::add_pair(pairs, i, planes, columns, kind);
 }
 
+// ---- edge support (ga_edges.h): the same walk with one atomic add per counted node crossing; the crossings of the host's list ----------
+__global__ void __launch_bounds__(64) ga_pileup_edges_kernel(gaed::EdgesLaunch P)
+{
+	__shared__ gao::OpsLds lds;
+	gaed::run_wave(P, lds, blockIdx.x, gridDim.x);
+}
+__global__ void __launch_bounds__(256) ga_pileup_slots_kernel(const uint32_t* slots, uint64_t n, uint32_t* counts, uint64_t entries)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i < n) gaed::add_slot(slots, i, counts, entries);
+}
+
 // every job's output record starts a run as "not run" (what a job keeps when no pass ever picks it up)
 __global__ void ga_outs_init_kernel(GaJobOut* outs, uint32_t n)
 {
@@ -363,15 +376,17 @@ struct PinnedPool
 	~PinnedPool() { for (auto& b : idle) hipHostFree(b.second); }
 };
 
-// the counters of one pileup: kind planes of one 32-bit word per column, in the HBM of the graph's device
+// the counters of one pileup: `nPlanes` planes of one 32-bit word per entry (ga_backend.h: a column, or a slot for the EDGES kind), in the
+// HBM of the graph's device; the EDGES kind keeps its mirror-slot table next to them
 struct DevPileup : GaBackendPileup
 {
 	int device = 0;
-	uint32_t kind = 0;
-	uint64_t columns = 0;
+	uint32_t kind = 0, nPlanes = 0;
+	uint64_t entries = 0;
 	uint32_t* planes = nullptr;
-	~DevPileup() override { hipSetDevice(device); if (planes) hipFree(planes); }
-	size_t bytes() const { return (size_t)kind * columns * 4; }
+	uint32_t* mirror = nullptr;
+	~DevPileup() override { hipSetDevice(device); if (planes) hipFree(planes); if (mirror) hipFree(mirror); }
+	size_t bytes() const { return (size_t)nPlanes * entries * 4; }
 	int reset() override
 	{
 		// (the caller lets no add into this pileup run at the same time -- ga_pileup_reset holds the pileup exclusively -- and an add has
@@ -383,10 +398,10 @@ struct DevPileup : GaBackendPileup
 	}
 	int download(uint64_t first, uint64_t n, uint32_t* out) const override
 	{
-		if (first > columns || n > columns - first) return GA_E_INVALID;
+		if (first > entries || n > entries - first) return GA_E_INVALID;
 		HIP_OK(hipSetDevice(device));
 		// (an add has finished on its batch's stream when addToPileup returns: nothing to wait for)
-		for (uint32_t k = 0; k < kind && n; k++) HIP_OK(hipMemcpy(out + (size_t)k * n, planes + (size_t)k * columns + first, n * 4, hipMemcpyDeviceToHost));
+		for (uint32_t k = 0; k < nPlanes && n; k++) HIP_OK(hipMemcpy(out + (size_t)k * n, planes + (size_t)k * entries + first, n * 4, hipMemcpyDeviceToHost));
 		return 0;
 	}
 };
@@ -397,13 +412,22 @@ struct DevGraph : GaBackendGraph
 	bool buildsMatchWords() const override { return true; }
 	bool codesOps() const override { return true; }
 	bool codesPileup() const override { return true; }
-	GaBackendPileup* createPileup(int kind, int* status) override
+	GaBackendPileup* createPileup(const GaPileupSpec& spec, int* status) override
 	{
+		*status = GA_E_INVALID;
+		const bool edges = spec.kind == GA_KIND_EDGES;
+		if (spec.planes == 0 || spec.planes != ga_pileup_planes_of_kind(spec.kind) || spec.entries != ga_pileup_entries(spec.kind, totalBp, edgeSlots)) return nullptr;
+		if (edges && (!spec.mirrorSlot || spec.entries >= 0xffffffffull)) return nullptr;
 		*status = GA_E_DEVICE;
 		if (hipSetDevice(device) != hipSuccess) return nullptr;
 		std::unique_ptr<DevPileup> p(new DevPileup());
-		p->device = device; p->kind = (uint32_t)kind; p->columns = totalBp;
+		p->device = device; p->kind = (uint32_t)spec.kind; p->nPlanes = spec.planes; p->entries = spec.entries;
 		if (hipMalloc((void**)&p->planes, std::max<size_t>(p->bytes(), 16)) != hipSuccess) { p->planes = nullptr; (void)hipGetLastError(); return nullptr; }
+		if (edges)
+		{
+			if (hipMalloc((void**)&p->mirror, std::max<size_t>((size_t)p->entries * 4, 16)) != hipSuccess) { p->mirror = nullptr; (void)hipGetLastError(); return nullptr; }
+			if (p->entries && hipMemcpy(p->mirror, spec.mirrorSlot, (size_t)p->entries * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+		}
 		if (p->reset() != 0) return nullptr;
 		*status = 0;
 		return p.release();
@@ -451,6 +475,7 @@ struct DevGraph : GaBackendGraph
 	std::vector<void*> allocs;
 	int cus = 0;
 	uint64_t totalBp = 0;
+	uint64_t edgeSlots = 0;            // the in-neighbour lists' total length: the entries of a pileup of the EDGES kind
 	// scratch pool owned by the graph: batches reuse it instead of allocating tens of GB each
 	uint8_t* pool = nullptr;
 	size_t poolBytes = 0;
@@ -1220,9 +1245,10 @@ struct DevBatch : GaBackendBatch
 	int addToPileup(GaBackendPileup* to, const GaPileupAdd& add, GaPileupAddOut& out) override
 	{
 		DevPileup* p = static_cast<DevPileup*>(to);
-		if (!cfg.emit_pileup || !p || p->device != g->device || p->columns != g->totalBp) return GA_E_INVALID;
+		if (!cfg.emit_pileup || !p || p->device != g->device || p->entries != ga_pileup_entries((int)p->kind, g->totalBp, g->edgeSlots)) return GA_E_INVALID;
 		out = GaPileupAddOut();
-		if (!add.nList && !add.nPairs) return 0;
+		const bool edges = p->kind == (uint32_t)GA_KIND_EDGES;
+		if (!add.nList && !(edges ? add.nSlots : add.nPairs)) return 0;
 		// everything that can refuse the add is looked at before a block is taken or anything is put on the stream
 		const uint32_t* twin = nullptr;
 		if (add.nList)
@@ -1242,12 +1268,16 @@ struct DevBatch : GaBackendBatch
 		if (blocks.jobList) release(blocks.jobList);
 		if (blocks.lut) release(blocks.lut);
 		if (blocks.pairs) release(blocks.pairs);
+		if (blocks.slots) release(blocks.slots);
 		return rc;
 	}
-	struct AddBlocks { uint32_t* jobList = nullptr; uint64_t* pairs = nullptr; uint8_t* lut = nullptr; unsigned long long* added = nullptr; };
+	struct AddBlocks { uint32_t* jobList = nullptr; uint64_t* pairs = nullptr; uint32_t* slots = nullptr; uint8_t* lut = nullptr; unsigned long long* added = nullptr; };
 	int addWith(DevPileup* p, const GaPileupAdd& add, const uint32_t* twin, GaPileupAddOut& out, AddBlocks& blocks)
 	{
 		uint32_t*& dJobList = blocks.jobList; uint64_t*& dPairs = blocks.pairs; uint8_t*& dLut = blocks.lut; unsigned long long*& dAdded = blocks.added;
+		// the EDGES kind takes the host's crossings (slot indices) where the other kinds take its items (plane, column)
+		const bool edges = p->kind == (uint32_t)GA_KIND_EDGES;
+		const size_t nPairs = edges ? 0 : add.nPairs, nSlots = edges ? add.nSlots : 0;
 		if (alloc(&dAdded, 1)) return GA_E_DEVICE;
 		HIP_OK(hipMemsetAsync(dAdded, 0, 8, stream));
 		if (add.nList)
@@ -1256,13 +1286,35 @@ struct DevBatch : GaBackendBatch
 			HIP_OK(hipMemcpyAsync(dJobList, add.list, add.nList * 4, hipMemcpyHostToDevice, stream));
 			HIP_OK(hipMemcpyAsync(dLut, opsLut, 256, hipMemcpyHostToDevice, stream));
 		}
-		if (add.nPairs)
+		if (nPairs)
 		{
-			if (alloc(&dPairs, add.nPairs)) return GA_E_DEVICE;
-			HIP_OK(hipMemcpyAsync(dPairs, add.pairs, add.nPairs * 8, hipMemcpyHostToDevice, stream));
+			if (alloc(&dPairs, nPairs)) return GA_E_DEVICE;
+			HIP_OK(hipMemcpyAsync(dPairs, add.pairs, nPairs * 8, hipMemcpyHostToDevice, stream));
+		}
+		if (nSlots)
+		{
+			if (alloc(&blocks.slots, nSlots)) return GA_E_DEVICE;
+			HIP_OK(hipMemcpyAsync(blocks.slots, add.slots, nSlots * 4, hipMemcpyHostToDevice, stream));
 		}
 		HIP_OK(hipEventRecord(evU[0], stream));
-		if (add.nList)
+		if (add.nList && edges)
+		{
+			gaed::EdgesLaunch P;
+			memset(&P, 0, sizeof(P));
+			gao::OpsLaunch& O = P.walk;
+			O.graph = L.graph; O.jobs = L.jobs; O.outs = L.outs; O.fills = resFills;
+			O.traces = L.traces; O.trace_bytes = L.trace_pool_cap;
+			O.seq = resSeq; O.seq_bytes = resSeqBytes; O.row_code = dLut;
+			O.twin = twin;
+			O.n_jobs = (uint32_t)jobs.size();
+			P.counts = p->planes; P.mirror = p->mirror; P.entries = p->entries;
+			P.list = dJobList; P.n_list = (uint32_t)add.nList; P.added = dAdded;
+			uint32_t waves = (uint32_t)std::min<size_t>(add.nList, (size_t)g->cus * 16);
+			if (knobs.waveSlots) waves = std::min(waves, knobs.waveSlots);
+			hipLaunchKernelGGL(ga_pileup_edges_kernel, dim3(waves), dim3(64), 0, stream, P);
+			HIP_OK(hipGetLastError());
+		}
+		else if (add.nList)
 		{
 			gapl::PileupLaunch P;
 			memset(&P, 0, sizeof(P));
@@ -1272,7 +1324,7 @@ struct DevBatch : GaBackendBatch
 			O.seq = resSeq; O.seq_bytes = resSeqBytes; O.row_code = dLut;
 			O.twin = twin;
 			O.n_jobs = (uint32_t)jobs.size();
-			P.planes = p->planes; P.columns = p->columns; P.kind = p->kind;
+			P.planes = p->planes; P.columns = p->entries; P.kind = p->kind;
 			P.list = dJobList; P.n_list = (uint32_t)add.nList; P.added = dAdded;
 			uint32_t waves = (uint32_t)std::min<size_t>(add.nList, (size_t)g->cus * 16);
 			if (knobs.waveSlots) waves = std::min(waves, knobs.waveSlots);
@@ -1280,9 +1332,14 @@ struct DevBatch : GaBackendBatch
 			else hipLaunchKernelGGL(ga_pileup_depth_kernel, dim3(waves), dim3(64), 0, stream, P);
 			HIP_OK(hipGetLastError());
 		}
-		if (add.nPairs)
+		if (nPairs)
 		{
-			hipLaunchKernelGGL(ga_pileup_pairs_kernel, dim3((uint32_t)((add.nPairs + 255) / 256)), dim3(256), 0, stream, dPairs, (uint64_t)add.nPairs, p->planes, p->columns, p->kind);
+			hipLaunchKernelGGL(ga_pileup_pairs_kernel, dim3((uint32_t)((nPairs + 255) / 256)), dim3(256), 0, stream, dPairs, (uint64_t)nPairs, p->planes, p->entries, p->kind);
+			HIP_OK(hipGetLastError());
+		}
+		if (nSlots)
+		{
+			hipLaunchKernelGGL(ga_pileup_slots_kernel, dim3((uint32_t)((nSlots + 255) / 256)), dim3(256), 0, stream, blocks.slots, (uint64_t)nSlots, p->planes, p->entries);
 			HIP_OK(hipGetLastError());
 		}
 		HIP_OK(hipEventRecord(evU[1], stream));
@@ -1299,10 +1356,11 @@ struct DevBatch : GaBackendBatch
 			const GaJobOut& o = outs[job];
 			if (o.status == GA_OK && o.n_valid > 0 && o.reserved3 != 1) { out.jobs++; out.moves += o.trace_len; }
 		}
-		for (size_t k = 0; k < add.nPairs; k++)
-			if (ga_pileup_plane_in_kind(p->kind, (uint32_t)(add.pairs[k] >> 56)) < p->kind && (add.pairs[k] & 0x00ffffffffffffffull) < p->columns) out.items++;
+		for (size_t k = 0; k < nPairs; k++)
+			if (ga_pileup_plane_in_kind(p->kind, (uint32_t)(add.pairs[k] >> 56)) < p->nPlanes && (add.pairs[k] & 0x00ffffffffffffffull) < p->entries) out.items++;
+		for (size_t k = 0; k < nSlots; k++) if (add.slots[k] < p->entries) out.items++;
 		if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: pileup: %llu jobs, %llu moves, %llu items (%zu from the host), %.2f ms\n",
-		                               (unsigned long long)out.jobs, (unsigned long long)out.moves, (unsigned long long)out.items, add.nPairs, ms);
+		                               (unsigned long long)out.jobs, (unsigned long long)out.moves, (unsigned long long)out.items, nPairs + nSlots, ms);
 		return 0;
 	}
 
@@ -1408,6 +1466,7 @@ GaBackendGraph* ga_backend_upload_graph(const GaFlatGraph& flat, const GaHmmTabl
 	g->g.n_nodes = (uint32_t)(flat.node_start.size() - 1);
 	g->g.reserved = 0;
 	g->totalBp = flat.node_start.back();
+	g->edgeSlots = ga_edge_slot_count(flat);
 	int bad = 0;
 	bad |= g->put(flat.node_start, &g->g.node_start);
 	bad |= g->put(flat.seq2, &g->g.seq2);

@@ -348,15 +348,46 @@ int ga_graph_node_columns(const ga_graph_t* g, int64_t digraphId, uint64_t* firs
 	return GA_S_OK;
 }
 
+int ga_graph_edge_slot_count(const ga_graph_t* g, uint64_t* n)
+{
+	if (!g || !n || !g->finalized) return GA_E_INVALID;
+	*n = ga_edge_slot_count(g->flat);
+	return GA_S_OK;
+}
+
+int ga_graph_edge_slots(const ga_graph_t* g, uint64_t first, uint64_t n, int64_t* fromIds, int64_t* toIds)
+{
+	if (!g || !g->finalized || (n && (!fromIds || !toIds))) return GA_E_INVALID;
+	const uint64_t slots = ga_edge_slot_count(g->flat);
+	if (first > slots || n > slots - first) return GA_E_INVALID;
+	// the node whose in-list holds slot `first`, then onward: slots are the in-lists laid end to end in node-index order
+	const std::vector<uint32_t>& off = g->flat.in_off;
+	uint32_t to = (uint32_t)(std::upper_bound(off.begin(), off.end(), (uint32_t)first) - off.begin());
+	to = to ? to - 1 : 0;
+	for (uint64_t k = 0; k < n; k++)
+	{
+		const uint32_t slot = (uint32_t)(first + k);
+		while (to + 1 < off.size() && off[to + 1] <= slot) to++;
+		fromIds[k] = g->ids[g->flat.in_nbr[slot]];
+		toIds[k] = g->ids[to];
+	}
+	return GA_S_OK;
+}
+
 int ga_pileup_create(const ga_graph_t* g, int kind, ga_pileup_t** out)
 {
-	if (!g || !out || !g->finalized || !g->device || (kind != GA_PILEUP_DEPTH && kind != GA_PILEUP_BASES)) return GA_E_INVALID;
+	if (!g || !out || !g->finalized || !g->device || (kind != GA_PILEUP_DEPTH && kind != GA_PILEUP_BASES && kind != GA_PILEUP_EDGES)) return GA_E_INVALID;
+	GaPileupSpec spec;
+	spec.kind = kind; spec.planes = ga_pileup_planes_of_kind(kind);
+	spec.entries = ga_pileup_entries(kind, g->bases.size(), ga_edge_slot_count(g->flat));
+	std::vector<uint32_t> mirror;
+	if (kind == GA_PILEUP_EDGES) { mirror = ga_edge_mirror_slots(g->flat, g->twin); mirror.resize(mirror.size() + 1, 0xffffffffu); spec.mirrorSlot = mirror.data(); }
 	int status = GA_S_OK;
-	GaBackendPileup* dev = g->device->createPileup(kind, &status);
+	GaBackendPileup* dev = g->device->createPileup(spec, &status);
 	if (!dev) return status ? status : GA_E_DEVICE;
 	ga_pileup* p = new ga_pileup();
-	p->g = g; p->kind = kind; p->dev = dev;
-	p->st.kind = kind; p->st.columns = g->bases.size();
+	p->g = g; p->kind = kind; p->planes = spec.planes; p->dev = dev;
+	p->st.kind = kind; p->st.columns = spec.entries;
 	*out = p;
 	return GA_S_OK;
 }
@@ -381,6 +412,7 @@ int ga_batch_pileup_add(ga_batch_t* b, ga_pileup_t* p)
 	GaPileupAdd add;
 	add.list = b->pileList.data(); add.nList = b->pileList.size();
 	add.pairs = b->pilePairs.data(); add.nPairs = b->pilePairs.size();
+	add.slots = b->pileSlots.data(); add.nSlots = b->pileSlots.size();
 	GaPileupAddOut o;
 	{
 		std::shared_lock<std::shared_mutex> shared(p->use);
@@ -397,8 +429,8 @@ int ga_batch_pileup_add(ga_batch_t* b, ga_pileup_t* p)
 int ga_pileup_download(const ga_pileup_t* p, uint64_t firstColumn, uint64_t nColumns, uint32_t* out)
 {
 	if (!p || (!out && nColumns)) return GA_E_INVALID;
-	const uint64_t columns = p->st.columns;
-	if (firstColumn > columns || nColumns > columns - firstColumn) return GA_E_INVALID;
+	const uint64_t entries = p->st.columns;              // (the entry count: columns, or slots for the EDGES kind)
+	if (firstColumn > entries || nColumns > entries - firstColumn) return GA_E_INVALID;
 	std::unique_lock<std::shared_mutex> alone(const_cast<ga_pileup*>(p)->use);      // (a whole add is in the copy or none of it)
 	return p->dev->download(firstColumn, nColumns, out);
 }

@@ -270,6 +270,7 @@ struct ga_batch
 	bool collected = false;
 	std::vector<uint32_t> pileList;
 	std::vector<uint64_t> pilePairs;
+	std::vector<uint32_t> pileSlots;      // ... and the crossings of those same reads as edge slots, for pileups of the EDGES kind
 	uint64_t pileFromDevice = 0, pileFromHost = 0;
 	~ga_batch() { delete dev; }
 };
@@ -279,6 +280,7 @@ struct ga_pileup
 {
 	const ga_graph* g = nullptr;
 	int kind = 0;
+	uint32_t planes = 0;                  // ga_pileup_planes_of_kind(kind); the entry count is st.columns
 	GaBackendPileup* dev = nullptr;
 	std::mutex lock;                      // (two batches may add at the same time: the statistics change hands under it)
 	std::shared_mutex use;                // adds share the counters (their adds are atomic); reset and download take them alone

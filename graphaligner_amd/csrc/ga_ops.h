@@ -105,7 +105,9 @@ GAO_FN bool self_loop(const GaDevGraph& g, uint32_t node)
 
 // what a walk does with the items it finds: count the runs of their types, write those runs at the job's scanned place, or hand every
 // item with its column to `sink` (ga_pileup.h), which then sees the left moves' cells too and no runs are formed
-enum { SINK_COUNT = 0, SINK_WRITE = 1, SINK_ADD = 2 };
+// SINK_EDGES (ga_edges.h): the items themselves are not looked at; every node crossing whose two cells both have an item is handed to
+// `sink` as the slot of the edge it takes (position in the in-neighbour lists laid end to end).  Its code is compiled into no other walk
+enum { SINK_COUNT = 0, SINK_WRITE = 1, SINK_ADD = 2, SINK_EDGES = 3 };
 struct NoSink { GAO_FN void item(uint32_t, uint64_t, uint32_t) {} };
 
 // the runs of one job: returns their number (SINK_ADD: 0)
@@ -133,6 +135,7 @@ template <int SINK, class Sink> GAO_FN uint32_t walk_job(const OpsLaunch& L, Ops
 	uint64_t base = 0, cnt = 0;
 	if (WRITE) { base = L.offsets[job]; cnt = L.offsets[job + 1] - base; }
 	uint32_t opened = 0, carryType = 0, carryLen = 0;       // runs opened so far; the open run
+	[[maybe_unused]] uint32_t prevRow = 0xffffffffu;        // SINK_EDGES: the row the round before's last move starts in (none yet: no row)
 	bool bad = false;
 	for (uint32_t m0 = 0; m0 < nMoves && !bad; m0 += 64)
 	{
@@ -186,6 +189,30 @@ template <int SINK, class Sink> GAO_FN uint32_t walk_job(const OpsLaunch& L, Ops
 		if (bad || top < totalCols) { bad = true; break; }     // (a node of length 0, or a move that names no in-neighbour: nothing the kernels write)
 		GAO_LANES(l) { if (l == 0) { lds.cNode[64] = node; lds.cTop[64] = top; lds.cLen[64] = len; lds.cCol0[64] = col0; } }
 		sync();
+		if constexpr (SINK == SINK_EDGES)
+		{
+			// the lane whose move is the column step numbered cTop of its cell crosses from `to`, the cell's node, into `from`, the next
+			// cell's: the edge from -> to, named by its place in to's in-list.  It counts when both cells have an item -- forward: the
+			// cells moves m and m + 1 start in (the stream's last cell has none); backward: the cells moves m - 1 and m lead to, where
+			// move m - 1 may be the round before's last (prevRow) --, neither lies on a dummy node and the two are not one column
+			GAO_LANES(l)
+			{
+				const uint32_t excl = lds.incl[l] - lds.own[l];
+				if ((uint32_t)l < nValid && (lds.own[l] >> 16) != 0 && (excl >> 16) == lds.cTop[l])
+				{
+					const uint32_t m = m0 + (uint32_t)l;
+					const uint32_t rowA = row0 - (excl & 0xffffu), rowB = rowA - (lds.own[l] & 0xffffu);
+					const uint32_t rowBefore = l == 0 ? prevRow : rowA + (lds.own[l > 0 ? l - 1 : 0] & 0xffffu);
+					const bool both = backward ? m > 0 && rowBefore < traceRows && rowA < traceRows : rowA < traceRows && rowB < traceRows && m + 1 < nMoves;
+					const uint32_t to = lds.cNode[l], from = lds.cNode[l + 1], last = G.n_nodes - 1;
+					if (both && to != 0 && to != last && from != 0 && from != last && !(to == from && lds.cLen[l] == 1))
+						sink.crossing(G.in_off[to] + ((uint32_t)lds.mv[l] >> 2), backward);
+				}
+			}
+			prevRow = row0 - ((lds.incl[63] - lds.own[63]) & 0xffffu);
+			top -= totalCols; row0 -= totalRows;
+			continue;
+		}
 		GAO_LANES(l)
 		{
 			uint32_t t = 0;

@@ -88,10 +88,11 @@ def run_overlapped(graph, inputs, bandwidth, ramp=0, flags=0, summary=False, gam
     are Python lists, per-read record arrays (summary=True) or the bytes of one GAM group per input (gam=True).
     find_seeds=dict(params=..., loci=...): an input whose seeds are None, and every ReadSet, becomes a seeded batch
     (Graph.prepare_seeded): seeding is then the first part of the stage in front of the kernels.
-    pileup=binding.Pileup (flags must have GA_F_PILEUP): every input is added to it after its collect, on that input's own stream, while the
-    next input's kernels run."""
+    pileup=binding.Pileup or a sequence of them (flags must have GA_F_PILEUP): every input is added to each after its collect, on that
+    input's own stream, while the next input's kernels run."""
     from concurrent.futures import ThreadPoolExecutor
     it = iter(inputs)
+    piles = [] if pileup is None else list(pileup) if isinstance(pileup, (list, tuple)) else [pileup]
 
     def prep():
         try:
@@ -112,8 +113,8 @@ def run_overlapped(graph, inputs, bandwidth, ramp=0, flags=0, summary=False, gam
         # (the batch is freed as soon as its results are out: its device buffers and its pinned copy of the reads serve the next one)
         try:
             res = batch.collect_gam() if gam else batch.collect(summary)
-            if pileup is not None:
-                pileup.add(batch)
+            for p in piles:
+                p.add(batch)
             return res
         finally:
             batch.close()
@@ -143,8 +144,8 @@ def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chu
                     concatenate (stream.hpp:24-63), so that is the GAM file of the whole read set, reads ordered longest first;
       otherwise     Python lists of per-read dicts (tests and small inputs: pickling 200 000 of those is not a transport).
     seeds=None with find_seeds=dict(params=..., loci=...): every chunk is a seeded batch (Graph.prepare_seeded).
-    pileup=binding.Pileup: this rank's chunks are added to it (run_overlapped); with several ranks each rank owns a pileup of its own
-    graph and the caller sums them."""
+    pileup=binding.Pileup or a sequence of them: this rank's chunks are added to each (run_overlapped); with several ranks each rank owns
+    pileups of its own graph and the caller sums them."""
     how = _seeding(seeds, find_seeds)
     chunks = make_chunks([len(r) for r in reads], chunk_reads)
     counter = _Counter(dist, tag)

@@ -280,9 +280,36 @@ int ga_batch_ops_stats(const ga_batch_t* b, ga_batch_ops_stats_t* out);
  * kernels) and issues one 32-bit atomic add per item; the two kinds of reads that GA_F_OPS takes from the host's TraceItem list (a byte
  * outside IUPAC -- such a read ends as an assertion and adds nothing --, and a forward part the reference leaves unshifted) add through
  * a list of (plane, column) pairs that ga_batch_collect keeps and a second, trivial kernel.  Integer adds: the result does not depend
- * on the order of batches or waves.  Memory: 4 * kind bytes per column in the HBM of the graph's device. */
+ * on the order of batches or waves.  Memory: 4 * K bytes per column in the HBM of the graph's device.
+ *
+ * KIND, PLANES, ENTRIES.  A pileup's kind names what it counts; its planes are the counters one entry has (8 for BASES, 1 for DEPTH and
+ * EDGES); its entries are what it counts over: the graph's columns for BASES and DEPTH, the graph's SLOTS for EDGES.  A kind constant is
+ * a name, not a size.
+ *
+ * THE RULE OF GA_PILEUP_EDGES (edge support: which edges the alignments cross).  One plane of uint32_t, one entry per slot.  Slots are the
+ * in-neighbour lists of the finalized graph laid end to end in node-index order (a bigraph node is its forward copy, then its reverse copy;
+ * within a list the order the edges were added in, a repeated edge once): slot in_off[node] + k is the edge from the node's k-th
+ * in-neighbour to the node.  ga_graph_edge_slot_count gives their number, ga_graph_edge_slots the digraph ids (from, to) of each; in-edges
+ * of the two dummy nodes, where a graph has them, are slots too and stay zero.  Adding a batch takes, for every read of the last collect
+ * with status == GA_S_OK and failed == 0, the same TraceItem list as above, cut at the SPLIT item into parts, and for every two
+ * consecutive items a, b of one part adds one at the slot of the directed edge (2 * a.node_id + a.reverse) -> (2 * b.node_id + b.reverse)
+ * when b's column is not a's column, b is not the next offset of the same digraph node, neither item lies on a dummy node, and that edge
+ * exists in the graph.  So the first cell of each part, which has no item, gives no crossing out of it and nothing is counted across the
+ * SPLIT (up to three crossings per read); a turn through a self-loop on a one-base node stays in its column and is not counted; a turn
+ * from the last offset of a longer self-loop node to its offset 0 is.  Edges are per strand like columns: a backward part counts on the
+ * other strand's edge twin(to) -> twin(from), and nothing is folded on the device (an edge a -> b and its mirror b ^ 1 -> a ^ 1 are one
+ * edge of the bigraph; the caller sums the two).  Counters wrap modulo 2^32.  Over a split graph the slots are the pieces' edges.
+ * Where it is made: the same walk over the same move bytes, on the same GA_F_PILEUP batches (no other prepare flag; one batch may be
+ * added to a BASES, a DEPTH and an EDGES pileup in turn), with one 32-bit atomic add per counted crossing; the reads taken from the host's
+ * list add through a list of slot indices.  Memory: 4 bytes per slot for the counters and 4 more for the mirror-slot table (the slot of
+ * the other strand's copy of each edge), both in the HBM of the graph's device. */
 #define GA_PILEUP_DEPTH 1
 #define GA_PILEUP_BASES 8
+#define GA_PILEUP_EDGES 32
+/* the slots of a finalized graph (no device needed): their number, and the digraph ids of n slots from `first` (GA_E_INVALID for a range
+ * past the slot count) */
+int ga_graph_edge_slot_count(const ga_graph_t* g, uint64_t* n_slots);
+int ga_graph_edge_slots(const ga_graph_t* g, uint64_t first, uint64_t n, int64_t* from_ids, int64_t* to_ids);
 typedef struct ga_pileup ga_pileup_t;
 /* zeroed; GA_E_INVALID for another kind or a graph that is not uploaded or whose back end has no pileups, GA_E_DEVICE when it does not
  * fit.  A pileup is freed before its graph. */
@@ -295,7 +322,8 @@ int ga_pileup_reset(ga_pileup_t* p);
  * not been collected since its last run, or belongs to another graph.  Calling it twice adds twice.  It runs on the batch's own stream
  * and returns when the add is done; two batches may add into one pileup at the same time from two threads, because the adds are atomic. */
 int ga_batch_pileup_add(ga_batch_t* b, ga_pileup_t* p);
-/* out[plane * n_columns + i] = entry (plane, first_column + i); GA_E_INVALID for a range outside the graph */
+/* out[plane * n_columns + i] = entry (plane, first_column + i), for every plane of the kind; the range is in entries -- columns, or slots
+ * for GA_PILEUP_EDGES -- and GA_E_INVALID when it leaves them */
 int ga_pileup_download(const ga_pileup_t* p, uint64_t first_column, uint64_t n_columns, uint32_t* out);
 typedef struct ga_pileup_stats {
 	double add_kernel_ms;        /* HIP-event time of the last add's kernel(s) */
@@ -305,7 +333,7 @@ typedef struct ga_pileup_stats {
 	uint64_t jobs_walked, moves_read;
 	uint64_t items_added;        /* from both sources; equals the sum over all entries as long as no counter wrapped */
 	int32_t kind, reserved;
-	uint64_t columns;
+	uint64_t columns;            /* the entry count: the graph's columns, or its slots for GA_PILEUP_EDGES */
 } ga_pileup_stats_t;
 int ga_pileup_stats(const ga_pileup_t* p, ga_pileup_stats_t* out);
 
