@@ -150,6 +150,16 @@ class AlignerParams:
         self.opsFile = ""           # --ops-out: per aligned read its operations (GA_F_OPS): counts, identity and the run string
         self.pileupFile = ""        # --pileup-out: per graph base that any aligned read touches, the eight counts of a pileup (GA_F_PILEUP)
         self.edgeSupportFile = ""   # --edge-support-out: per edge of the bigraph that any aligned read crosses, its count (a pileup of kind "edges")
+        # --sites-out: the columns of a BASES pileup that pass the thresholds, selected on the device (Pileup.sites): --sites-min-depth,
+        # --sites-min-alt, --sites-frac NUM/DEN; --sites-fold folds the two strands onto the forward copies
+        self.sitesFile = ""
+        self.sitesMinDepth = 1
+        self.sitesMinAlt = 0
+        self.sitesFrac = (0, 1)
+        self.sitesFold = False
+        # --supported-edges-out: the edges of the bigraph whose folded count is >= --min-edge-support, from one fold query on the device
+        self.supportedEdgesFile = ""
+        self.minEdgeSupport = 1
 
 
 def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr):
@@ -163,7 +173,9 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
     flags = binding.GA_F_TRACE | (binding.GA_F_OPS if getattr(params, "opsFile", "") else 0)
     want_pileup = bool(getattr(params, "pileupFile", ""))
     want_edges = bool(getattr(params, "edgeSupportFile", ""))
-    if want_pileup or want_edges:
+    want_sites = bool(getattr(params, "sitesFile", ""))
+    want_supported = bool(getattr(params, "supportedEdgesFile", ""))
+    if want_pileup or want_edges or want_sites or want_supported:
         flags |= binding.GA_F_PILEUP
     find_seeds = getattr(params, "findSeeds", False)
     if params.seedFile == "" and not find_seeds:
@@ -215,8 +227,8 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
     order = list(range(len(reads)))[::-1]
     with_seeds = [i for i in order if i in seeds_of]
     results = {}
-    pile = graph.pileup("bases") if want_pileup else None
-    edge_pile = graph.pileup("edges") if want_edges else None
+    pile = graph.pileup("bases") if want_pileup or want_sites else None
+    edge_pile = graph.pileup("edges") if want_edges or want_supported else None
     piles = [p for p in (pile, edge_pile) if p is not None]       # (one flagged batch is added to each in turn)
     if find_seeds and seeded is not None:
         try:
@@ -293,10 +305,14 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
                 cells = c["match"] + c["mismatch"] + c["insertion"] + c["deletion"]
                 f.write("%s\t%d\t%d\t%d\t%d\t%.6f\t%s\n" % (rd.seq_id, c["match"], c["mismatch"], c["insertion"], c["deletion"],
                                                              c["match"] / cells if cells else 0.0, binding.ops_string(r["ops"])))
-    if pile is not None:
+    if want_pileup:
         write_pileup(params.pileupFile, pile, [r for r in results.values() if r["status"] == 0 and not r["failed"]])
-    if edge_pile is not None:
+    if want_edges:
         write_edge_support(params.edgeSupportFile, edge_pile)
+    if want_sites:
+        write_sites(params.sitesFile, pile, params.sitesFold, params.sitesMinDepth, params.sitesMinAlt, params.sitesFrac)
+    if want_supported:
+        write_supported_edges(params.supportedEdgesFile, edge_pile, params.minEdgeSupport)
     return [(rd.seq_id, r) for rd, r in written]
 
 
@@ -313,6 +329,23 @@ def write_edge_support(path, pile):
     total = int(pile.stats()["items_added"])
     if written != total:
         raise RuntimeError("edge support: %d counts written, %d items added to the pileup" % (written, total))
+
+
+def write_sites(path, pile, fold, min_depth, min_alt, frac):
+    """one line per site of the query (Pileup.sites: selected on the device, neither the planes nor a TraceItem list come down): node id,
+    strand (+ / -), offset, graph base, then the eight counts -- folded onto the forward copy with `fold` --, in entry order"""
+    sites = pile.sites(fold=fold, min_depth=min_depth, min_alt=min_alt, alt_frac=frac)
+    with open(path, "w") as f:
+        for s in sites:
+            f.write("%d\t%s\t%d\t%s\t%s\n" % (int(s["node_id"]), "-" if s["reverse"] else "+", int(s["offset"]), s["graph_char"].decode(),
+                                                "\t".join(str(int(c)) for c in s["counts"])))
+
+
+def write_supported_edges(path, pile, min_support):
+    """the lines of write_edge_support restricted to a folded count >= min_support, from one fold query (Pileup.supported_edges)"""
+    with open(path, "w") as f:
+        for (a, b), c in sorted(pile.supported_edges(min_support).items()):
+            f.write("%d %d %d %d %d\n" % (a >> 1, a & 1, b >> 1, b & 1, c))
 
 
 def write_pileup(path, pile, aligned):
@@ -346,7 +379,8 @@ def parse_args(argv, err=sys.stderr):
     p = AlignerParams()
     initial_full_band = False
     coord_given = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out=", "pileup-out=", "edge-support-out="])
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out=", "pileup-out=", "edge-support-out=",
+                                                             "sites-out=", "sites-min-depth=", "sites-min-alt=", "sites-frac=", "sites-fold", "supported-edges-out=", "min-edge-support="])
     for o, a in opts:
         if o == "-g":
             p.graphFile = a
@@ -387,12 +421,31 @@ def parse_args(argv, err=sys.stderr):
             p.pileupFile = a
         elif o == "--edge-support-out":
             p.edgeSupportFile = a
+        elif o == "--sites-out":
+            p.sitesFile = a
+        elif o == "--sites-min-depth":
+            p.sitesMinDepth = int(a)
+        elif o == "--sites-min-alt":
+            p.sitesMinAlt = int(a)
+        elif o == "--sites-frac":
+            num, _, den = a.partition("/")
+            p.sitesFrac = (int(num), int(den) if den else 1)
+        elif o == "--sites-fold":
+            p.sitesFold = True
+        elif o == "--supported-edges-out":
+            p.supportedEdgesFile = a
+        elif o == "--min-edge-support":
+            p.minEdgeSupport = int(a)
 
     def stop(msg):
         err.write(msg + "\n")
         raise SystemExit(0)
     if p.dynamicRowStart % 64 != 0:
         stop("dynamic row start has to be a multiple of 64")
+    if p.sitesMinDepth < 1 or p.sitesMinAlt < 0 or not (0 <= p.sitesFrac[0] <= p.sitesFrac[1] and 1 <= p.sitesFrac[1] <= 65535):
+        stop("--sites-min-depth must be >= 1 and --sites-frac NUM/DEN a fraction of at most 1 with DEN of 1..65535")
+    if p.minEdgeSupport < 1:
+        stop("--min-edge-support must be >= 1")
     if p.numThreads < 1:
         stop("number of threads must be >= 1")
     if p.initialBandwidth < 2:

@@ -21,6 +21,7 @@ GA_PILEUP_DEPTH = 1
 GA_PILEUP_BASES = 8
 GA_PILEUP_EDGES = 32
 # kind, planes and entries are three things (include/graphaligner_amd.h, "pileups"): the counters one entry has, per kind
+GA_SITES_FOLD = 1
 PILEUP_KINDS = {"bases": GA_PILEUP_BASES, "depth": GA_PILEUP_DEPTH, "edges": GA_PILEUP_EDGES}
 PILEUP_PLANES_OF_KIND = {GA_PILEUP_BASES: 8, GA_PILEUP_DEPTH: 1, GA_PILEUP_EDGES: 1}
 PILEUP_PLANES = ("match", "mismatch_A", "mismatch_C", "mismatch_G", "mismatch_T", "mismatch_other", "deletion", "insertion")
@@ -199,6 +200,10 @@ def load(path=None):
     if hasattr(L, "ga_graph_edge_slots"):                                  # (bench.py --lib may name a build from before edge support)
         L.ga_graph_edge_slot_count.argtypes = [C.c_void_p, C.c_void_p]
         L.ga_graph_edge_slots.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    if hasattr(L, "ga_pileup_sites"):                                      # (bench.py --lib may name a build from before site queries)
+        L.ga_pileup_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ga_sites_free.argtypes = [C.c_void_p]
+        L.ga_sites_free.restype = None
     if hasattr(L, "ga_find_seeds"):
         L.ga_seed_params_default.argtypes = [C.c_void_p]
         L.ga_seed_params_default.restype = None
@@ -495,6 +500,28 @@ class ReadSet:
         self.total_bp = sum(len(r) for r in self._keep)
 
 
+class GaSiteParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("alt_num", C.c_uint32), ("alt_den", C.c_uint32), ("reserved", C.c_uint32), ("min_depth", C.c_uint64),
+                ("min_alt", C.c_uint64), ("first_entry", C.c_uint64), ("n_entries", C.c_uint64), ("max_sites", C.c_uint64)]
+
+
+class GaSites(C.Structure):
+    _fields_ = [("n_sites", C.c_uint64), ("n_total", C.c_uint64), ("entries_scanned", C.c_uint64), ("kernel_ms", C.c_double), ("sites", C.c_void_p)]
+
+
+# ga_site_t as a numpy record
+SITE_DTYPE = np.dtype([("entry", "<u8"), ("counts", "<u4", (8,)), ("node_id", "<i8"), ("offset", "<u4"), ("reverse", "u1"), ("graph_char", "S1"),
+                       ("reserved", "u1", (2,)), ("from_id", "<i8"), ("to_id", "<i8")])
+assert SITE_DTYPE.itemsize == 72
+
+
+class SiteArray(np.ndarray):
+    """the records of Pileup.sites() with the query's totals"""
+    total = 0
+    kernel_ms = 0.0
+    entries_scanned = 0
+
+
 class Pileup:
     """ga_pileup_t: `planes` planes of uint32 counters over `entries` entries -- the graph's columns, or its edge slots for the kind
     "edges" --, in the HBM of the graph's device.  `kind_id` is the library's constant of the kind: a name, not a size"""
@@ -538,6 +565,44 @@ class Pileup:
         if self.kind != "edges":
             raise ValueError("edge_support: not a pileup of kind 'edges'")
         return fold_edge_support(self.g.edge_slots(), self.counts()[0])
+
+    def sites(self, fold=True, min_depth=1, min_alt=0, alt_frac=(0, 1), first=0, n=None, max_sites=0):
+        """the entries that pass the thresholds, both strands folded when `fold` (include/graphaligner_amd.h: "pileup sites"), selected
+        on the device: a structured array (SITE_DTYPE) in ascending entry order, with .total = the sites found (more than len() when
+        max_sites cut them), .kernel_ms and .entries_scanned"""
+        if not hasattr(self.L, "ga_pileup_sites"):
+            raise RuntimeError("this library has no site queries")
+        q = GaSiteParams()
+        q.flags = GA_SITES_FOLD if fold else 0
+        q.alt_num, q.alt_den = int(alt_frac[0]), int(alt_frac[1])
+        q.min_depth, q.min_alt = int(min_depth), int(min_alt)
+        q.first_entry = int(first)
+        q.n_entries = self.entries - int(first) if n is None else int(n)
+        q.max_sites = int(max_sites)
+        res = C.POINTER(GaSites)()
+        _check(self.L, self.L.ga_pileup_sites(self.h, C.byref(q), C.byref(res)), "ga_pileup_sites")
+        try:
+            r = res.contents
+            out = np.zeros(int(r.n_sites), dtype=SITE_DTYPE).view(SiteArray)
+            if r.n_sites:
+                C.memmove(out.ctypes.data, r.sites, int(r.n_sites) * SITE_DTYPE.itemsize)
+            out.total, out.kernel_ms, out.entries_scanned = int(r.n_total), float(r.kernel_ms), int(r.entries_scanned)
+        finally:
+            self.L.ga_sites_free(res)
+        return out
+
+    def supported_edges(self, min_support=1):
+        """kind "edges": the dict of edge_support() restricted to the edges of the bigraph whose folded count is >= min_support (>= 1),
+        from one fold query on the device instead of a download of every slot"""
+        if self.kind != "edges":
+            raise ValueError("supported_edges: not a pileup of kind 'edges'")
+        if int(min_support) < 1:
+            raise ValueError("supported_edges: min_support must be at least 1")
+        out = {}
+        for s in self.sites(fold=True, min_depth=int(min_support)):
+            a, b = int(s["from_id"]), int(s["to_id"])
+            out[min((a, b), (b ^ 1, a ^ 1))] = int(s["counts"][0])
+        return out
 
     def node(self, node_id, reverse=False):
         """(planes, length) array of the node's columns, offset 0 first"""

@@ -142,6 +142,23 @@ inline std::vector<uint32_t> ga_edge_mirror_slots(const GaFlatGraph& f, const st
 	return mirror;
 }
 
+// ---- site queries (ga_sites.h): fold the two strands' counters and keep the entries that pass a threshold ------------------------------
+// one site as the back end leaves it: the entry and its folded counts (planes the kind does not have are 0)
+struct GaSiteRec { uint64_t entry; uint32_t counts[8]; };
+// the per-node fold table of a columns query: the node of the other strand (0x7fffffff: none) | 0x80000000 on a forward copy
+constexpr uint32_t GA_FOLD_NONE = 0x7fffffffu, GA_FOLD_FORWARD = 0x80000000u;
+// a query the host has validated (include/graphaligner_amd.h: ga_site_params_t); foldTable: fold queries over a columns kind only, one
+// word per node, the same array at every query of a graph (a back end may keep its copy)
+struct GaSiteQuery
+{
+	bool fold = false;
+	uint64_t min_depth = 1, min_alt = 0;
+	uint32_t alt_num = 0, alt_den = 1;
+	uint64_t first = 0, n = 0, max_sites = 0;
+	const uint32_t* foldTable = nullptr; size_t nNodes = 0;
+};
+struct GaSitesOut { std::vector<GaSiteRec> recs; uint64_t n_total = 0; double kernel_ms = 0; };
+
 class GaBackendPileup
 {
 public:
@@ -149,6 +166,8 @@ public:
 	virtual int reset() = 0;
 	// out[plane * n + i] = the counter of (plane, first + i), for every plane of the kind; first + n <= entries
 	virtual int download(uint64_t first, uint64_t n, uint32_t* out) const = 0;
+	// the sites of the query in ascending entry order, the first max_sites of them; a back end without it refuses (100 = GA_E_INVALID)
+	virtual int sites(const GaSiteQuery&, GaSitesOut&) { return 100; }
 };
 
 // ---- seeding (ga_seed.h): a k-mer index of the uploaded graph and, per batch of reads, the seeds it gives ------------------------

@@ -23,6 +23,7 @@
 #include "ga_ops.h"
 #include "ga_pileup.h"
 #include "ga_edges.h"
+#include "ga_sites.h"
 
 namespace {
 
@@ -356,6 +357,17 @@ __global__ void __launch_bounds__(256) ga_pileup_slots_kernel(const uint32_t* sl
 	if (i < n) gaed::add_slot(slots, i, counts, entries);
 }
 
+// ---- site queries (ga_sites.h): one streaming pass over a pileup's planes marks the sites, a scan places them, a second pass writes them ----
+__global__ void __launch_bounds__(64) ga_pileup_sites_mark_kernel(gast::SitesLaunch L)
+{
+	__shared__ gast::SitesLds lds;
+	gast::mark_wave(L, lds, blockIdx.x, gridDim.x);
+}
+__global__ void __launch_bounds__(64) ga_pileup_sites_write_kernel(gast::SitesLaunch L)
+{
+	gast::write_wave(L, blockIdx.x, gridDim.x);
+}
+
 // every job's output record starts a run as "not run" (what a job keeps when no pass ever picks it up)
 __global__ void ga_outs_init_kernel(GaJobOut* outs, uint32_t n)
 {
@@ -378,8 +390,10 @@ struct PinnedPool
 
 // the counters of one pileup: `nPlanes` planes of one 32-bit word per entry (ga_backend.h: a column, or a slot for the EDGES kind), in the
 // HBM of the graph's device; the EDGES kind keeps its mirror-slot table next to them
+struct DevGraph;
 struct DevPileup : GaBackendPileup
 {
+	DevGraph* g = nullptr;             // (a pileup is freed before its graph)
 	int device = 0;
 	uint32_t kind = 0, nPlanes = 0;
 	uint64_t entries = 0;
@@ -404,6 +418,10 @@ struct DevPileup : GaBackendPileup
 		for (uint32_t k = 0; k < nPlanes && n; k++) HIP_OK(hipMemcpy(out + (size_t)k * n, planes + (size_t)k * entries + first, n * 4, hipMemcpyDeviceToHost));
 		return 0;
 	}
+	// (below DevGraph, whose block list, node table and stream it uses)
+	int sites(const GaSiteQuery& q, GaSitesOut& out) override;
+	struct SiteBlocks { std::vector<std::pair<size_t, void*>> taken; };
+	int sitesWith(const GaSiteQuery& q, GaSitesOut& out, SiteBlocks& blocks);
 };
 
 struct DevGraph : GaBackendGraph
@@ -421,7 +439,7 @@ struct DevGraph : GaBackendGraph
 		*status = GA_E_DEVICE;
 		if (hipSetDevice(device) != hipSuccess) return nullptr;
 		std::unique_ptr<DevPileup> p(new DevPileup());
-		p->device = device; p->kind = (uint32_t)spec.kind; p->nPlanes = spec.planes; p->entries = spec.entries;
+		p->g = this; p->device = device; p->kind = (uint32_t)spec.kind; p->nPlanes = spec.planes; p->entries = spec.entries;
 		if (hipMalloc((void**)&p->planes, std::max<size_t>(p->bytes(), 16)) != hipSuccess) { p->planes = nullptr; (void)hipGetLastError(); return nullptr; }
 		if (edges)
 		{
@@ -467,6 +485,12 @@ struct DevGraph : GaBackendGraph
 	uint32_t* dTwin = nullptr;
 	uint8_t* dRev = nullptr;
 	uint32_t* dOpsTwin = nullptr;      // the twin table alone, for GA_F_OPS batches of ga_batch_prepare (uploaded at the first of them)
+	// site queries (ga_sites.h): the per-node fold table, uploaded at the first fold query over a columns kind, freed with the graph; the
+	// stream and the two events the queries run on (one query at a time: sitesLock)
+	std::mutex sitesLock;
+	uint32_t* dFold = nullptr;
+	hipStream_t sitesStream = nullptr;
+	hipEvent_t evS[2] = {nullptr, nullptr};
 	GaBackendBatch* beginSeededBatch(const GaSeededRequest& req, GaSeededPlan& plan, int* status) override;
 
 	int device = 0;
@@ -487,6 +511,8 @@ struct DevGraph : GaBackendGraph
 		for (auto& b : idleBlocks) hipFree(b.second);
 		if (pool) hipFree(pool);
 		if (hostPool) hipHostFree(hostPool);
+		for (hipEvent_t e : evS) if (e) hipEventDestroy(e);
+		if (sitesStream) hipStreamDestroy(sitesStream);
 	}
 	// device buffers of the batches (match words, jobs, outputs, trace pool): handed back here instead of hipFree'd, because hipFree
 	// waits for the whole device -- i.e. for the kernels of whatever batch is running -- and the stages of consecutive batches are
@@ -567,6 +593,92 @@ struct DevGraph : GaBackendGraph
 		return 0;
 	}
 };
+
+// ---- site queries (ga_sites.h) -----------------------------------------------------------------------------------------------------
+int DevPileup::sites(const GaSiteQuery& q, GaSitesOut& out)
+{
+	out = GaSitesOut();
+	const bool edges = kind == (uint32_t)GA_KIND_EDGES, foldNodes = q.fold && !edges;
+	if (!g || q.first > entries || q.n > entries - q.first || q.alt_den == 0) return GA_E_INVALID;
+	if (foldNodes && (!q.foldTable || q.nNodes != g->g.n_nodes)) return GA_E_INVALID;
+	if (q.fold && edges && !mirror) return GA_E_INVALID;
+	if (q.n == 0) return 0;
+	std::lock_guard<std::mutex> one(g->sitesLock);
+	HIP_OK(hipSetDevice(device));
+	if (!g->sitesStream) HIP_OK(hipStreamCreateWithFlags(&g->sitesStream, hipStreamNonBlocking));
+	for (hipEvent_t& e : g->evS) if (!e) HIP_OK(hipEventCreate(&e));
+	if (foldNodes && !g->dFold)
+	{
+		void* t = nullptr;
+		HIP_OK(hipMalloc(&t, std::max<size_t>(q.nNodes * 4, 16)));
+		g->allocs.push_back(t);
+		HIP_OK(hipMemcpy(t, q.foldTable, q.nNodes * 4, hipMemcpyHostToDevice));
+		g->dFold = (uint32_t*)t;
+	}
+	SiteBlocks blocks;
+	const int rc = sitesWith(q, out, blocks);
+	// the blocks go back to the graph's list whether or not the query went through (after an error, once the stream is idle)
+	if (rc) (void)hipStreamSynchronize(g->sitesStream);
+	for (auto& b : blocks.taken) g->giveBlock(b.second, b.first);
+	return rc;
+}
+
+int DevPileup::sitesWith(const GaSiteQuery& q, GaSitesOut& out, SiteBlocks& blocks)
+{
+	hipStream_t stream = g->sitesStream;
+	auto take = [&](size_t bytes) -> void* {
+		bytes = std::max<size_t>((bytes + 255) & ~(size_t)255, 256);
+		void* p = g->takeBlock(bytes);
+		if (p) blocks.taken.emplace_back(bytes, p);
+		return p;
+	};
+	gast::SitesLaunch L;
+	memset(&L, 0, sizeof(L));
+	L.planes = planes; L.entries = entries; L.kind = kind; L.nPlanes = nPlanes;
+	L.fold = q.fold ? 1u : 0u; L.n_nodes = g->g.n_nodes;
+	L.node_start = g->g.node_start; L.fold_table = g->dFold; L.mirror = mirror;
+	L.first = q.first; L.n = q.n;
+	L.min_depth = q.min_depth; L.min_alt = q.min_alt; L.alt_num = q.alt_num; L.alt_den = q.alt_den;
+	L.n_tiles = (q.n + gast::kTile - 1) / gast::kTile;
+	const size_t nT = (size_t)L.n_tiles;
+	uint64_t* dCounts = (uint64_t*)take((nT + 1) * 8);
+	uint64_t* dOffsets = (uint64_t*)take((nT + 1) * 8);
+	L.mask = (uint64_t*)take(nT * gast::kRounds * 8);
+	if (!dCounts || !dOffsets || !L.mask) return GA_E_DEVICE;
+	L.counts = dCounts; L.offsets = dOffsets;
+	size_t tmpBytes = 0;
+	HIP_OK(rocprim::exclusive_scan(nullptr, tmpBytes, dCounts, dOffsets, (uint64_t)0, nT + 1, rocprim::plus<uint64_t>(), stream));
+	void* dTmp = take(tmpBytes + 16);
+	if (!dTmp) return GA_E_DEVICE;
+	HIP_OK(hipMemsetAsync(dCounts + nT, 0, 8, stream));
+	// enough waves to keep the memory system busy: a wave has 8 (fold: 16) loads of 256 bytes in flight
+	const uint32_t waves = (uint32_t)std::min<uint64_t>(L.n_tiles, (uint64_t)std::max(g->cus, 1) * 32);
+	HIP_OK(hipEventRecord(g->evS[0], stream));
+	hipLaunchKernelGGL(ga_pileup_sites_mark_kernel, dim3(waves), dim3(64), 0, stream, L);
+	HIP_OK(hipGetLastError());
+	HIP_OK(rocprim::exclusive_scan(dTmp, tmpBytes, dCounts, dOffsets, (uint64_t)0, nT + 1, rocprim::plus<uint64_t>(), stream));
+	uint64_t total = 0;
+	HIP_OK(hipMemcpyAsync(&total, dOffsets + nT, 8, hipMemcpyDeviceToHost, stream));
+	HIP_OK(hipStreamSynchronize(stream));
+	if (total > q.n) return GA_E_DEVICE;
+	const uint64_t nRecs = q.max_sites ? std::min(total, q.max_sites) : total;
+	if (nRecs)
+	{
+		L.recs = (GaSiteRec*)take((size_t)nRecs * sizeof(GaSiteRec));
+		if (!L.recs) return GA_E_DEVICE;
+		L.n_recs = nRecs;
+		hipLaunchKernelGGL(ga_pileup_sites_write_kernel, dim3(waves), dim3(64), 0, stream, L);
+		HIP_OK(hipGetLastError());
+	}
+	HIP_OK(hipEventRecord(g->evS[1], stream));
+	out.recs.resize((size_t)nRecs);
+	if (nRecs) HIP_OK(hipMemcpyAsync(out.recs.data(), L.recs, (size_t)nRecs * sizeof(GaSiteRec), hipMemcpyDeviceToHost, stream));
+	HIP_OK(hipStreamSynchronize(stream));
+	float ms = 0;
+	HIP_OK(hipEventElapsedTime(&ms, g->evS[0], g->evS[1]));
+	out.n_total = total; out.kernel_ms = ms;
+	return 0;
+}
 
 // the few switches the library reads from the environment, once per batch: GA_LANES (1 / 0: force which kernel goes first -- the GPU
 // parity tests run every case both ways), GA_DEBUG_PASSES (one line per launch on stderr) and two test hooks: the trace pool's size

@@ -443,6 +443,98 @@ int ga_pileup_stats(const ga_pileup_t* p, ga_pileup_stats_t* out)
 	return GA_S_OK;
 }
 
+// ---- pileup sites (include/graphaligner_amd.h: "pileup sites"; ga_sites.h) ---------------------------------------------------------
+
+// the fold table of a columns query (ga_backend.h: GA_FOLD_*) and the fold's preconditions: overlap 0, and every node but the dummy
+// ones has a twin that is another node, of its length, with its reverse complement as bases.  Looked at once per graph
+static bool foldTableOf(const ga_graph* g, const uint32_t** table)
+{
+	std::lock_guard<std::mutex> guard(g->foldLock);
+	if (g->foldState == 0)
+	{
+		const uint32_t n = g->nodeCount();
+		bool ok = g->dbgOverlap == 0 && g->twin.size() == n && g->idOdd.size() == n;
+		std::vector<uint32_t> t(n, GA_FOLD_NONE);
+		for (uint32_t i = 1; ok && i + 1 < n; i++)
+		{
+			const uint32_t o = g->twin[i];
+			if (o == 0 || o >= n - 1 || o == i || g->twin[o] != i || g->nodeLen(o) != g->nodeLen(i)) { ok = false; break; }
+			const uint32_t len = g->nodeLen(i);
+			const uint64_t a = g->nodeStart[i], b = g->nodeStart[o];
+			for (uint32_t k = 0; ok && k < len; k++) ok = g->bases[a + k] <= 3 && g->bases[b + (len - 1 - k)] == 3 - g->bases[a + k];
+			t[i] = o | (g->idOdd[i] ? 0u : GA_FOLD_FORWARD);
+		}
+		g->foldTable.swap(t);
+		g->foldState = ok ? 1 : -1;
+	}
+	*table = g->foldTable.data();
+	return g->foldState == 1;
+}
+
+int ga_pileup_sites(ga_pileup_t* p, const ga_site_params_t* q, ga_sites_t** out)
+{
+	if (!p || !q || !out) return GA_E_INVALID;
+	*out = nullptr;
+	const uint64_t entries = p->st.columns;
+	if ((q->flags & ~GA_SITES_FOLD) || q->min_depth < 1 || q->alt_den < 1 || q->alt_den > 65535 || q->alt_num > q->alt_den) return GA_E_INVALID;
+	if (q->first_entry > entries || q->n_entries > entries - q->first_entry) return GA_E_INVALID;
+	const ga_graph* g = p->g;
+	const bool edges = p->kind == GA_PILEUP_EDGES;
+	GaSiteQuery dq;
+	dq.fold = (q->flags & GA_SITES_FOLD) != 0;
+	dq.min_depth = q->min_depth; dq.min_alt = q->min_alt; dq.alt_num = q->alt_num; dq.alt_den = q->alt_den;
+	dq.first = q->first_entry; dq.n = q->n_entries; dq.max_sites = q->max_sites;
+	if (dq.fold && !edges)
+	{
+		if (!foldTableOf(g, &dq.foldTable)) return GA_E_INVALID;
+		dq.nNodes = g->nodeCount();
+	}
+	GaSitesOut got;
+	{
+		std::unique_lock<std::shared_mutex> alone(p->use);   // (a whole add is in what the query reads or none of it)
+		if (int s = p->dev->sites(dq, got)) return s;
+	}
+	const uint64_t cap = dq.max_sites ? std::min<uint64_t>(dq.max_sites, got.n_total) : got.n_total;
+	if (got.recs.size() != cap) return GA_E_DEVICE;
+	std::unique_ptr<ga_sites_t> res(new ga_sites_t());
+	res->n_sites = got.recs.size(); res->n_total = got.n_total; res->entries_scanned = dq.n; res->kernel_ms = got.kernel_ms;
+	res->sites = res->n_sites ? new ga_site_t[(size_t)res->n_sites]() : nullptr;
+	// the records' places in the graph: entries ascend, so the node (or the in-list) of each is found from the one before onward
+	const std::vector<uint32_t>& inOff = g->flat.in_off;
+	for (size_t k = 0; k < got.recs.size(); k++)
+	{
+		const GaSiteRec& r = got.recs[k];
+		ga_site_t& s = res->sites[k];
+		s.entry = r.entry;
+		memcpy(s.counts, r.counts, sizeof(s.counts));
+		if (r.entry >= entries || (k && r.entry <= got.recs[k - 1].entry)) { ga_sites_free(res.release()); return GA_E_DEVICE; }
+		if (edges)
+		{
+			const uint32_t to = (uint32_t)(std::upper_bound(inOff.begin(), inOff.end(), (uint32_t)r.entry) - inOff.begin()) - 1;
+			s.from_id = g->ids[g->flat.in_nbr[(size_t)r.entry]];
+			s.to_id = g->ids[to];
+			s.graph_char = '-';
+		}
+		else
+		{
+			const uint32_t node = (uint32_t)(std::upper_bound(g->nodeStart.begin(), g->nodeStart.end(), r.entry) - g->nodeStart.begin()) - 1;
+			s.node_id = g->ids[node] / 2;
+			s.offset = (uint32_t)(r.entry - g->nodeStart[node]);
+			s.reverse = (uint8_t)(g->ids[node] & 1);
+			s.graph_char = g->baseChar(node, s.offset);
+		}
+	}
+	*out = res.release();
+	return GA_S_OK;
+}
+
+void ga_sites_free(ga_sites_t* s)
+{
+	if (!s) return;
+	delete[] s->sites;
+	delete s;
+}
+
 const char* ga_status_string(int s)
 {
 	switch (s)

@@ -199,6 +199,11 @@ struct ga_graph
 	// (0xffffffff: there is none), and digraph id & 1
 	std::vector<uint32_t> twin;
 	std::vector<uint8_t> idOdd;
+	// site queries that fold columns (ga_sites.h): the per-node fold table and whether the graph meets the fold's preconditions, made
+	// at the first such query (0: not looked at yet, 1: folds, -1: does not)
+	mutable std::mutex foldLock;
+	mutable int foldState = 0;
+	mutable std::vector<uint32_t> foldTable;
 	// optional node splitting (ga_graph_load_gfa_split): piece bigraph id -> the node it was cut from
 	struct Piece { int64_t orig; uint64_t start, len, origLen; };
 	std::unordered_map<int64_t, Piece> pieces;

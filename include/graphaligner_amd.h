@@ -337,6 +337,72 @@ typedef struct ga_pileup_stats {
 } ga_pileup_stats_t;
 int ga_pileup_stats(const ga_pileup_t* p, ga_pileup_stats_t* out);
 
+/* ---- pileup sites: both strands folded and entries selected on the device --------------------------------- */
+/* THE RULE.  A site query reads a pileup's counters where they lie in HBM and returns the entries that pass a threshold, so that the
+ * download is proportional to the number of sites and not to the graph.  It is defined on the pileup's counters P (plane p of entry e:
+ * Pp[e]) and the graph alone.  The query takes ga_site_params_t; GA_E_INVALID unless flags is 0 or GA_SITES_FOLD, min_depth >= 1,
+ * 1 <= alt_den <= 65535, alt_num <= alt_den and [first_entry, first_entry + n_entries) lies inside the pileup's entries (min_alt: any
+ * value; max_sites 0: no cap).
+ *
+ * CANDIDATES AND FOLDED COUNTS F[0 .. planes).  All sums are uint32_t, modulo 2^32, like the counters.
+ *   BASES and DEPTH, flags 0: every column c of the range is a candidate; F[p] = Pp[c].
+ *   BASES and DEPTH, GA_SITES_FOLD: the candidates are the columns of the range that lie on a node with an even digraph id (the forward
+ *   copies; the two dummy nodes are no candidates, their counters are zero by the rule of the pileups).  The partner of column c of
+ *   `node`, whose other strand is `twin` (digraph id ^ 1) and whose length is len, is c' = node_start[twin] + len - 1 - (c - node_start[node]).
+ *     BASES: F[0] = P0[c] + P0[c'];  F[p] = Pp[c] + P(5-p)[c'] for p = 1..4, which maps A <-> T and C <-> G because a read on the reverse
+ *     copy carries the complement;  F[5], F[6], F[7] = the same plane's sum.
+ *     DEPTH: F[0] = P0[c] + P0[c'].
+ *   Preconditions of the fold over columns, checked on the host once per graph and remembered: the graph was finalized with overlap 0 and
+ *   every node but the two dummy nodes has a twin of the same length whose bases are its reverse complement; otherwise GA_E_INVALID.  (With
+ *   an overlap > 0 the two strands are trimmed at different ends: equal length is then not enough for c' to be the same base.)
+ *   Known limit: an INSERTION of a read on the reverse strand is counted at the column that read stays in, whose mirror is one base to the
+ *   right of the column at which a forward read would count the same insertion; plane 7 is folded as it is.
+ *   EDGES, flags 0: every slot s of the range is a candidate; F[0] = count[s].
+ *   EDGES, GA_SITES_FOLD: with m the mirror slot of s (the slot of twin(to) -> twin(from), the table the pileup keeps; none where that
+ *   node or edge does not exist), s is a candidate when m is none or s <= m;  F[0] = count[s] + count[m] when m exists and m != s, else
+ *   count[s].  (No precondition: a graph of one strand has no mirror slots and folds to itself.)
+ *
+ * SELECTION, in 64-bit arithmetic.  D = F[0] + ... + F[6] for BASES and F[0] for the other kinds; X = max(D - F[0], F[7]) for BASES and 0
+ * for the other kinds.  A candidate is a site when D >= min_depth and X >= min_alt and X * alt_den >= alt_num * D.  So min_alt = 0,
+ * alt_num = 0 gives every covered entry; min_alt = 1, alt_num = 0 every entry where a read differs; EDGES with min_depth = t the edges
+ * supported t times.
+ *
+ * RESULT.  The sites in ascending entry order, the first max_sites of them; n_total is how many there were.  The order comes from a
+ * scan over per-tile counts, never from an atomic: two calls on the same counters return identical bytes.  Every site carries its entry,
+ * counts[8] = F (planes the kind does not have are 0) and what the host finds by binary search in its own node table: for the columns
+ * kinds the bigraph node_id (digraph id / 2), offset, reverse (digraph id & 1) and graph_char (the base of the graph at the column,
+ * '-' on a dummy node); for EDGES the digraph ids from_id and to_id of the slot.
+ * The call holds the pileup exclusively like ga_pileup_download: it waits for adds in flight and holds new ones back.  Each rank's
+ * pileup is its own: nothing here merges the pileups of several devices. */
+#define GA_SITES_FOLD 1u
+typedef struct ga_site_params {
+	uint32_t flags;              /* 0 or GA_SITES_FOLD */
+	uint32_t alt_num, alt_den;   /* the fraction alt_num / alt_den of the depth that X must reach */
+	uint32_t reserved;
+	uint64_t min_depth, min_alt;
+	uint64_t first_entry, n_entries;
+	uint64_t max_sites;          /* 0: no cap */
+} ga_site_params_t;
+typedef struct ga_site {
+	uint64_t entry;
+	uint32_t counts[8];
+	int64_t node_id;             /* columns kinds: bigraph id;  EDGES: 0 */
+	uint32_t offset;
+	uint8_t reverse;
+	char graph_char;
+	uint8_t reserved[2];
+	int64_t from_id, to_id;      /* EDGES: digraph ids;  columns kinds: 0 */
+} ga_site_t;
+typedef struct ga_sites {
+	uint64_t n_sites;            /* records in `sites` */
+	uint64_t n_total;            /* sites the query found (>= n_sites when max_sites cut them) */
+	uint64_t entries_scanned;
+	double kernel_ms;            /* HIP events over both launches and the scan between them */
+	ga_site_t* sites;
+} ga_sites_t;
+int ga_pileup_sites(ga_pileup_t* p, const ga_site_params_t* params, ga_sites_t** out);
+void ga_sites_free(ga_sites_t* s);
+
 /* ---- seeds found on the device ------------------------------------------------------------------------- */
 /* A k-mer index of the uploaded graph and, per batch of reads, up to max_seeds seeds per read in the form ga_align_batch takes.  The rule
  * (DESIGN.md section 10 has it in full): keys are 2 bits per base (A=0 C=1 G=2 T=3, first base most significant); a k-mer is kept when the
