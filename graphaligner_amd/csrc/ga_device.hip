@@ -1,5 +1,6 @@
 // ga_device.hip -- the gfx950 back end (ga_backend.h), one translation unit.  This file holds the kernels: a __global__ wrapper around
-// each device program -- the extension program one wave per read (ga_kernel.h; state in LDS, or in HBM for bands of up to 4 096 nodes,
+// each device program -- the extension program one wave per read (ga_kernel.h, which brings ga_sparse.h and ga_job.h with run_job;
+// the three wrappers build their Slot with makeSlot; state in LDS, or in HBM for bands of up to 4 096 nodes,
 // with or without the sparse method) and one lane per read (ga_lanes.h), the match words, the job plan of seeded batches (ga_plan.h),
 // the walk over finished jobs' moves as operations, pileups and edge support (ga_ops.h, ga_pileup.h, ga_edges.h) and the site queries
 // (ga_sites.h); seeding brings its own (ga_seed_dev.h).  The extension kernels are persistent launches: a wave per scratch slot in HBM,
@@ -65,15 +66,9 @@ __host__ __device__ inline SlotLayout slotLayout(uint32_t capCols, uint32_t maxS
 	return l;
 }
 
-#ifndef GA_WAVES_EU
-#define GA_WAVES_EU 4
-#endif
-template <int MAXN, bool GENERAL, bool SPARSE = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GA_WAVES_EU, 8))) ga_extend_kernel(GaLaunch L)
+// a wave's views of its scratch slot (sparse: the variant carries the sparse method, so its tables and override windows are laid out)
+__device__ __forceinline__ gak::Slot makeSlot(const GaLaunch& L, uint8_t* base, const SlotLayout& lay, bool sparse)
 {
-	__shared__ gak::WaveState<MAXN> ws;
-	const SlotLayout lay = slotLayout(L.cap_cols, L.max_slices, L.arena_words, L.trace_cap, SPARSE ? L.sparse_bw : 0u);
-	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.slot_bytes;
 	gak::Slot slot;
 	slot.end_prev = (uint32_t*)(base + lay.endPrev);
 	slot.end_cur = (uint32_t*)(base + lay.endCur);
@@ -83,9 +78,21 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GA_WAVE
 	slot.slice_flags = base + lay.flags;
 	slot.ckpt = (uint32_t*)(base + lay.ckpt);
 	slot.below_off = (uint32_t*)(base + lay.belowOff);
-	slot.sparse = SPARSE ? base + lay.sparse : nullptr;
-	slot.ovr = SPARSE ? (uint32_t*)(base + lay.ovr) : nullptr;
-	slot.sparse_max_bw = SPARSE ? L.sparse_bw : 0u;
+	slot.sparse = sparse ? base + lay.sparse : nullptr;
+	slot.ovr = sparse ? (uint32_t*)(base + lay.ovr) : nullptr;
+	slot.sparse_max_bw = sparse ? L.sparse_bw : 0u;
+	return slot;
+}
+#ifndef GA_WAVES_EU
+#define GA_WAVES_EU 4
+#endif
+template <int MAXN, bool GENERAL, bool SPARSE = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GA_WAVES_EU, 8))) ga_extend_kernel(GaLaunch L)
+{
+	__shared__ gak::WaveState<MAXN> ws;
+	const SlotLayout lay = slotLayout(L.cap_cols, L.max_slices, L.arena_words, L.trace_cap, SPARSE ? L.sparse_bw : 0u);
+	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.slot_bytes;
+	const gak::Slot slot = makeSlot(L, base, lay, SPARSE);
 	while (true)
 	{
 		uint32_t k = gaw::wave_atomic_add(L.next_job, 1u);
@@ -107,18 +114,7 @@ __global__ void __launch_bounds__(64) ga_wide_kernel(GaLaunch L)
 	const SlotLayout lay = slotLayout(L.cap_cols, L.max_slices, L.arena_words, L.trace_cap, 0u, sizeof(gak::WaveState<kWideNodes>));
 	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.slot_bytes;
 	gak::WaveState<kWideNodes>& ws = *(gak::WaveState<kWideNodes>*)(base + lay.state);
-	gak::Slot slot;
-	slot.end_prev = (uint32_t*)(base + lay.endPrev);
-	slot.end_cur = (uint32_t*)(base + lay.endCur);
-	slot.slice_off = (uint32_t*)(base + lay.sliceOff);
-	slot.arena = (uint32_t*)(base + lay.arena);
-	slot.trace = base + lay.trace;
-	slot.slice_flags = base + lay.flags;
-	slot.ckpt = (uint32_t*)(base + lay.ckpt);
-	slot.below_off = (uint32_t*)(base + lay.belowOff);
-	slot.sparse = nullptr;
-	slot.ovr = nullptr;
-	slot.sparse_max_bw = 0u;
+	const gak::Slot slot = makeSlot(L, base, lay, false);
 	while (true)
 	{
 		uint32_t k = gaw::wave_atomic_add(L.next_job, 1u);
@@ -138,18 +134,7 @@ __global__ void __launch_bounds__(64) ga_wide_sparse_kernel(GaLaunch L)
 	const SlotLayout lay = slotLayout(L.cap_cols, L.max_slices, L.arena_words, L.trace_cap, L.sparse_bw, sizeof(gak::WaveState<kWideNodes>), kWideNodes);
 	uint8_t* base = L.scratch + (uint64_t)blockIdx.x * L.slot_bytes;
 	gak::WaveState<kWideNodes>& ws = *(gak::WaveState<kWideNodes>*)(base + lay.state);
-	gak::Slot slot;
-	slot.end_prev = (uint32_t*)(base + lay.endPrev);
-	slot.end_cur = (uint32_t*)(base + lay.endCur);
-	slot.slice_off = (uint32_t*)(base + lay.sliceOff);
-	slot.arena = (uint32_t*)(base + lay.arena);
-	slot.trace = base + lay.trace;
-	slot.slice_flags = base + lay.flags;
-	slot.ckpt = (uint32_t*)(base + lay.ckpt);
-	slot.below_off = (uint32_t*)(base + lay.belowOff);
-	slot.sparse = base + lay.sparse;
-	slot.ovr = (uint32_t*)(base + lay.ovr);
-	slot.sparse_max_bw = L.sparse_bw;
+	const gak::Slot slot = makeSlot(L, base, lay, true);
 	while (true)
 	{
 		uint32_t k = gaw::wave_atomic_add(L.next_job, 1u);
