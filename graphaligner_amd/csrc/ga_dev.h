@@ -1,6 +1,8 @@
 // ga_dev.h -- what the parts of the device back end share: the owners of what a stage borrows (events, a stream, blocks of the graph's
-// block list), the scan in its two steps, the graph and the pileup as they lie in HBM, and what every stage of a batch uses (BatchCore).
-// The stages themselves, each with its own state, are in ga_dev_prepare.h, ga_dev_ladder.h and ga_dev_post.h.
+// block list, a device allocation of its own: DevBuf, GrownBuf), the scan and the sort in their two steps, the graph and the pileup as
+// they lie in HBM, and what every stage of a batch uses (BatchCore).
+// The stages themselves, each with its own state, are in ga_dev_prepare.h, ga_dev_ladder.h and ga_dev_post.h; the seed engine, which the
+// graph holds, is ga_dev_seed.h, included here between the owners and the graph.
 // Not a header for others: a part of ga_device.hip's translation unit, included once below its kernels.
 #ifndef GA_DEVICE_PARTS
 #error "ga_dev.h is a part of ga_device.hip"
@@ -38,6 +40,58 @@ template <typename T> struct Scan
 	int size(hipStream_t stream) { HIP_OK(rocprim::exclusive_scan(nullptr, tmpBytes, in, out, (T)0, n, rocprim::plus<T>(), stream)); return 0; }
 	int run(void* tmp, hipStream_t stream) { HIP_OK(rocprim::exclusive_scan(tmp, tmpBytes, in, out, (T)0, n, rocprim::plus<T>(), stream)); return 0; }
 };
+// rocprim's stable sort of n (key, value) pairs by the keys' bits [0, bits), in the same two steps
+template <typename K, typename V> struct SortPairs
+{
+	K* keysIn; K* keysOut; V* valsIn; V* valsOut; size_t n; unsigned bits;
+	size_t tmpBytes = 0;
+	int size(hipStream_t stream) { HIP_OK(rocprim::radix_sort_pairs(nullptr, tmpBytes, keysIn, keysOut, valsIn, valsOut, n, 0u, bits, stream)); return 0; }
+	int run(void* tmp, hipStream_t stream) { HIP_OK(rocprim::radix_sort_pairs(tmp, tmpBytes, keysIn, keysOut, valsIn, valsOut, n, 0u, bits, stream)); return 0; }
+};
+
+// one temporary device allocation of the seed engine (ga_dev_seed.h), freed when its scope ends, sooner by reset(), or handed over by
+// release().  Straight from hipMalloc and back to hipFree, not from the graph's block list: an index build holds tens of bytes per entry
+// for a moment, and the block list would keep such blocks idle (and never frees on a failed build).
+template <typename T> struct DevBuf
+{
+	T* p = nullptr;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() { reset(); }
+	int alloc(size_t count)
+	{
+		reset();
+		void* q = nullptr;
+		HIP_OK(hipMalloc(&q, count * sizeof(T)));
+		p = (T*)q;
+		return 0;
+	}
+	void reset() { if (p) hipFree(p); p = nullptr; }
+	T* release() { T* q = p; p = nullptr; return q; }
+	operator T*() const { return p; }
+};
+// a device buffer kept between calls and grown when needed: ensure() frees and reallocates only when the buffer is too small (then to
+// `room` bytes where that is more: head room), freed with its owner
+struct GrownBuf
+{
+	void* p = nullptr;
+	size_t bytes = 0;
+	GrownBuf() = default;
+	GrownBuf(const GrownBuf&) = delete;
+	GrownBuf& operator=(const GrownBuf&) = delete;
+	~GrownBuf() { if (p) hipFree(p); }
+	int ensure(size_t need, size_t room = 0)
+	{
+		if (need <= bytes) return 0;
+		if (p) hipFree(p);
+		p = nullptr; bytes = 0;
+		void* q = nullptr;
+		HIP_OK(hipMalloc(&q, std::max(need, room)));
+		p = q; bytes = std::max(need, room);
+		return 0;
+	}
+};
 
 // pinned host blocks for the batches' copies of the reads (page-locking half a GB per batch costs more than copying it): a block goes
 // back to the pool when the last holder -- the batch, or results whose edit sequences point into it -- lets go of it
@@ -47,6 +101,13 @@ struct PinnedPool
 	std::vector<std::pair<size_t, char*>> idle;
 	~PinnedPool() { for (auto& b : idle) hipHostFree(b.second); }
 };
+
+}  // namespace
+
+// the seed engine: it uses the owners above, and the graph below holds one and needs the complete type
+#include "ga_dev_seed.h"
+
+namespace {
 
 // the counters of one pileup: `nPlanes` planes of one 32-bit word per entry (ga_backend.h: a column, or a slot for the EDGES kind), in the
 // HBM of the graph's device; the EDGES kind keeps its mirror-slot table next to them

@@ -6,15 +6,20 @@
 // (ga_sites.h); seeding brings its own (ga_seed_dev.h).  The extension kernels are persistent launches: a wave per scratch slot in HBM,
 // pulling jobs from a device-side queue; waves share nothing but the queue counter and the trace pool's bump counter.
 // Below the kernels the host side is included in parts, and the entry points of ga_backend.h end the file:
-//   ga_dev.h          the graph resident in HBM with its pools and block list, the pileup, the owners of events, streams and blocks,
-//                     and what every stage of a batch uses (BatchCore)
+//   ga_dev.h          the graph resident in HBM with its pools and block list, the pileup, the owners of events, streams, blocks and
+//                     single device allocations, and what every stage of a batch uses (BatchCore)
+//   ga_dev_seed.h     the seed engine: the index and the topology coordinate built as named stages, the launches of the seeding kernels
+//                     (included by ga_dev.h between its owners, which the engine uses, and the graph, which holds the engine)
 //   ga_dev_prepare.h  a batch's prepare: reads, jobs and match words into device memory; the seeded prepare (BatchPrepared)
 //   ga_dev_ladder.h   a batch's run: the scratch geometry and the passes of the ladder, ga_ladder.h (BatchLadder)
 //   ga_dev_post.h     after the ladder: operations, pileup add, the results' way back (DevBatch); a pileup's site queries
 // A batch is built in these layers, each derived from the one before with its state next to its functions.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
