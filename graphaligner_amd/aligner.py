@@ -148,6 +148,7 @@ class AlignerParams:
         self.seedLoci = False       # --seed-loci: one seed per locus
         self.seedCoord = "file"     # --seed-coord: "file" or "topology"
         self.opsFile = ""           # --ops-out: per aligned read its operations (GA_F_OPS): counts, identity and the run string
+        self.correctedFile = ""     # --corrected-out: per aligned read the graph's bases along its alignment (GA_F_PATHSEQ), as FASTA
         self.pileupFile = ""        # --pileup-out: per graph base that any aligned read touches, the eight counts of a pileup (GA_F_PILEUP)
         self.edgeSupportFile = ""   # --edge-support-out: per edge of the bigraph that any aligned read crosses, its count (a pileup of kind "edges")
         # --sites-out: the columns of a BASES pileup that pass the thresholds, selected on the device (Pileup.sites): --sites-min-depth,
@@ -171,6 +172,9 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
     out.write("%d reads\n" % len(reads))
     # (GA_F_OPS only when its file is asked for: the other output is the same with and without it)
     flags = binding.GA_F_TRACE | (binding.GA_F_OPS if getattr(params, "opsFile", "") else 0)
+    # (nor GA_F_PATHSEQ)
+    if getattr(params, "correctedFile", ""):
+        flags |= binding.GA_F_PATHSEQ
     want_pileup = bool(getattr(params, "pileupFile", ""))
     want_edges = bool(getattr(params, "edgeSupportFile", ""))
     want_sites = bool(getattr(params, "sitesFile", ""))
@@ -305,6 +309,11 @@ def align_reads(params, device=0, lib_path=None, out=sys.stdout, err=sys.stderr)
                 cells = c["match"] + c["mismatch"] + c["insertion"] + c["deletion"]
                 f.write("%s\t%d\t%d\t%d\t%d\t%.6f\t%s\n" % (rd.seq_id, c["match"], c["mismatch"], c["insertion"], c["deletion"],
                                                              c["match"] / cells if cells else 0.0, binding.ops_string(r["ops"])))
+    if getattr(params, "correctedFile", ""):
+        # per aligned read, in output order: the backward part's bases and the forward part's on one line (nothing is stitched at the seed)
+        with open(params.correctedFile, "w") as f:
+            for rd, r in written:
+                f.write(">%s\n%s\n" % (rd.seq_id, r["path_seq"].decode()))
     if want_pileup:
         write_pileup(params.pileupFile, pile, [r for r in results.values() if r["status"] == 0 and not r["failed"]])
     if want_edges:
@@ -379,7 +388,7 @@ def parse_args(argv, err=sys.stderr):
     p = AlignerParams()
     initial_full_band = False
     coord_given = False
-    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out=", "pileup-out=", "edge-support-out=",
+    opts, _ = getopt.getopt(argv, "g:f:a:t:B:A:is:d:MSb:", ["find-seeds", "seed-k=", "seed-max=", "seed-walks=", "seed-loci", "seed-coord=", "ops-out=", "corrected-out=", "pileup-out=", "edge-support-out=",
                                                              "sites-out=", "sites-min-depth=", "sites-min-alt=", "sites-frac=", "sites-fold", "supported-edges-out=", "min-edge-support="])
     for o, a in opts:
         if o == "-g":
@@ -417,6 +426,8 @@ def parse_args(argv, err=sys.stderr):
             coord_given = True
         elif o == "--ops-out":
             p.opsFile = a
+        elif o == "--corrected-out":
+            p.correctedFile = a
         elif o == "--pileup-out":
             p.pileupFile = a
         elif o == "--edge-support-out":

@@ -17,6 +17,7 @@ STATUS = {0: "OK", 1: "ASSERTION", 2: "UNSUPPORTED_BAND", 3: "BAD_SEED", 10: "CA
 GA_F_TRACE = 1
 GA_F_OPS = 2
 GA_F_PILEUP = 4
+GA_F_PATHSEQ = 8
 GA_PILEUP_DEPTH = 1
 GA_PILEUP_BASES = 8
 GA_PILEUP_EDGES = 32
@@ -70,6 +71,21 @@ class GaResultsOps(C.Structure):
     """ga_results_t with the three fields GA_F_OPS fills at its end.  Results of batches without the flag are read through GaResults
     alone, so that a library from before those fields (bench.py --lib) is never read past its own struct."""
     _fields_ = GaResults._fields_ + [("read_ops", C.POINTER(GaReadOps)), ("n_ops", C.c_size_t), ("ops", C.POINTER(C.c_uint32))]
+
+
+class GaReadPathSeq(C.Structure):
+    _fields_ = [("first_base", C.c_uint64), ("n_bases", C.c_uint32), ("n_backward", C.c_uint32)]
+
+
+class GaResultsPathSeq(C.Structure):
+    """ga_results_t with the three fields GA_F_PATHSEQ fills behind those of GA_F_OPS.  Read only for batches with that flag, as
+    GaResultsOps is"""
+    _fields_ = GaResultsOps._fields_ + [("read_path_seq", C.POINTER(GaReadPathSeq)), ("n_path_bases", C.c_size_t), ("path_bases", C.POINTER(C.c_char))]
+
+
+class GaBatchPathSeqStats(C.Structure):
+    _fields_ = [("count_kernel_ms", C.c_double), ("write_kernel_ms", C.c_double), ("jobs_walked", C.c_uint64), ("moves_read", C.c_uint64),
+                ("bases_written", C.c_uint64), ("reads_from_device", C.c_uint64), ("reads_from_host", C.c_uint64)]
 
 
 class GaBatchOpsStats(C.Structure):
@@ -188,6 +204,8 @@ def load(path=None):
     L.ga_version.restype = C.c_char_p
     if hasattr(L, "ga_batch_ops_stats"):                                   # (bench.py --lib may name a build from before GA_F_OPS)
         L.ga_batch_ops_stats.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "ga_batch_path_seq_stats"):                              # (bench.py --lib may name a build from before GA_F_PATHSEQ)
+        L.ga_batch_path_seq_stats.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "ga_pileup_create"):                                     # (bench.py --lib may name a build from before GA_F_PILEUP)
         L.ga_graph_node_columns.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.ga_pileup_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -695,6 +713,15 @@ class Batch:
         _check(self.L, self.L.ga_batch_ops_stats(self.h, C.byref(st)), "ga_batch_ops_stats")
         return {k: getattr(st, k) for k, _ in st._fields_}
 
+    def path_seq_stats(self):
+        """ga_batch_path_seq_stats_t of a batch prepared with GA_F_PATHSEQ as a dict: the two kernels' times, jobs walked, moves read, bases
+        written and, from the last collect, how many reads got their bases from the device and from the host"""
+        if not hasattr(self.L, "ga_batch_path_seq_stats"):
+            raise RuntimeError("this library has no ga_batch_path_seq_stats")
+        st = GaBatchPathSeqStats()
+        _check(self.L, self.L.ga_batch_path_seq_stats(self.h, C.byref(st)), "ga_batch_path_seq_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
     def seeds(self):
         """the SeedResult a seeded batch was planned from (what Graph.find_seeds would have returned); an error for other batches"""
         out = C.POINTER(GaSeedSetLoci if self.loci else GaSeedSet)()
@@ -749,12 +776,17 @@ class Batch:
         """summary=True: per-read numpy record array only (status, failed, score, n_mappings, ...), no Python lists;
         unsplit=True: results of a graph loaded with split=... on the nodes of the GFA file (ga_results_unsplit).  A batch prepared
         with GA_F_OPS: every read's dict also has ops (uint32 array of shape (n, 2): type, length) and op_counts (dict of the four
-        summed lengths); with summary=True the return value is (records, op_counts array of shape (reads, 4), list of ops arrays)"""
+        summed lengths); with summary=True the return value is (records, op_counts array of shape (reads, 4), list of ops arrays).
+        A batch prepared with GA_F_PATHSEQ: every read's dict also has path_seq (bytes: the graph's bases along the alignment, the
+        backward part's first) and path_seq_backward (how many of them are the backward part's); with summary=True two more values
+        follow the others: the list of path_seq and an array of path_seq_backward"""
         want_ops = bool(self.flags & GA_F_OPS)
-        out = C.POINTER(GaResultsOps if want_ops else GaResults)()
+        want_path = bool(self.flags & GA_F_PATHSEQ)
+        struct = GaResultsPathSeq if want_path else GaResultsOps if want_ops else GaResults
+        out = C.POINTER(struct)()
         _check(self.L, self.L.ga_batch_collect(self.h, C.byref(out)), "ga_batch_collect")
         if unsplit:
-            merged = C.POINTER(GaResultsOps if want_ops else GaResults)()
+            merged = C.POINTER(struct)()
             try:
                 _check(self.L, self.L.ga_results_unsplit(self.g.h, out, C.byref(merged)), "ga_results_unsplit")
             finally:
@@ -769,16 +801,21 @@ class Batch:
                 assert dt.itemsize == C.sizeof(GaReadResult)
                 buf = C.string_at(R.reads, R.n_reads * dt.itemsize) if R.n_reads else b""
                 recs = np.frombuffer(buf, dtype=dt).copy()
-                if not want_ops:
+                if not want_ops and not want_path:
                     return recs
-                counts, runs = _unpack_ops(R)
-                return recs, counts, runs
+                extra = _unpack_ops(R) if want_ops else ()
+                return (recs,) + tuple(extra) + (_unpack_path_seq(R) if want_path else ())
             reads = _unpack(out.contents)
             if want_ops:
                 counts, runs = _unpack_ops(out.contents)
                 for i, r in enumerate(reads):
                     r["ops"] = runs[i]
                     r["op_counts"] = dict(match=int(counts[i, 0]), mismatch=int(counts[i, 1]), insertion=int(counts[i, 2]), deletion=int(counts[i, 3]))
+            if want_path:
+                seqs, n_backward = _unpack_path_seq(out.contents)
+                for i, r in enumerate(reads):
+                    r["path_seq"] = seqs[i]
+                    r["path_seq_backward"] = int(n_backward[i])
             return reads
         finally:
             self.L.ga_results_free(out)
@@ -822,6 +859,17 @@ def _unpack_ops(R):
         w = np.array(words[ro.first_op:ro.first_op + ro.n_ops], dtype=np.uint32)
         runs.append(np.stack([w & 7, w >> 3], axis=1).astype(np.uint32) if len(w) else np.zeros((0, 2), dtype=np.uint32))
     return counts, runs
+
+
+def _unpack_path_seq(R):
+    """(per read its path sequence as bytes, array of the backward parts' lengths)"""
+    n = R.n_reads
+    seqs, n_backward = [], np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        rp = R.read_path_seq[i]
+        seqs.append(C.string_at(C.addressof(R.path_bases.contents) + rp.first_base, rp.n_bases) if rp.n_bases else b"")
+        n_backward[i] = rp.n_backward
+    return seqs, n_backward
 
 
 def ops_string(ops):

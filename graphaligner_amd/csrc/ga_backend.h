@@ -55,6 +55,7 @@ struct GaRunConfig
 	uint32_t emit_runs = 0;             // 1: no result of the batch needs a cell list: the lanes = reads kernel hands back node runs instead of moves
 	uint32_t emit_ops = 0;              // 1: GA_F_OPS: after the last pass the back end codes every job's operations as runs (ga_ops.h)
 	uint32_t emit_pileup = 0;           // 1: GA_F_PILEUP: the batch keeps what addToPileup walks (the moves, the reads, the twin table); no launch in run
+	uint32_t emit_pathseq = 0;          // 1: GA_F_PATHSEQ: after the last pass (and the operations) the back end writes every job's path sequence (ga_pathseq.h)
 };
 
 struct GaRunStats
@@ -85,6 +86,11 @@ struct GaEqSource
 // of the job's part of the read's TraceItem list, each run type | length << 3; the HIP-event times of the counting and the writing launch;
 // the jobs coded and the moves read.  The arrays stay the back end's (valid from fetch until fetchDone or the next fetch)
 struct GaOpsOut { const uint32_t* runs = nullptr; const uint64_t* offsets = nullptr; uint64_t n_runs = 0; double count_ms = 0, write_ms = 0; uint64_t jobs = 0, moves = 0; };
+
+// What a batch run with GaRunConfig::emit_pathseq hands back (ga_pathseq.h): job j's bases are bases[offsets[j] .. offsets[j + 1]), ASCII, in
+// the final order of the job's part of the read's alignment; the HIP-event times of the counting and the writing launch; the jobs walked
+// and the moves read.  The arrays stay the back end's (valid from fetch until fetchDone or the next fetch)
+struct GaPathSeqOut { const uint8_t* bases = nullptr; const uint64_t* offsets = nullptr; uint64_t n_bases = 0; double count_ms = 0, write_ms = 0; uint64_t jobs = 0, moves = 0; };
 
 // ---- pileups (ga_pileup.h): counters per column of the graph that stay with the graph; batches add to them after their collect --------
 // what one add is given: the winning jobs (job index | 0x80000000 when the part has cells), longest first, and the items the host derived
@@ -262,6 +268,8 @@ public:
 	// pileups has no factory (100 = GA_E_INVALID) and a prepare with GA_F_PILEUP is refused on it
 	virtual GaBackendPileup* createPileup(const GaPileupSpec&, int* status) { *status = 100; return nullptr; }
 	virtual bool codesPileup() const { return false; }
+	// true: this back end writes path sequences (GaRunConfig::emit_pathseq); on one that does not, a prepare with GA_F_PATHSEQ is refused
+	virtual bool writesPathSeq() const { return false; }
 	// host memory for a batch's copy of the reads (the product: pinned blocks from a pool, so that their upload is one DMA transfer)
 	virtual std::shared_ptr<char> hostBlock(size_t bytes)
 	{
@@ -286,6 +294,8 @@ public:
 	virtual int fetch(std::vector<GaJobOut>& outs, const uint8_t** traceBytes, uint64_t* nBytes) = 0;
 	// after fetch, of a batch run with emit_ops: the runs, their places and the launches' times; a back end without it refuses
 	virtual int fetchOps(GaOpsOut&) { return 100; }
+	// after fetch, of a batch run with emit_pathseq: the bases, their places and the launches' times; a back end without it refuses
+	virtual int fetchPathSeq(GaPathSeqOut&) { return 100; }
 	virtual void fetchDone() {}
 	// of a batch run with emit_pileup, after fetch and until the next run: adds the listed jobs' items to a pileup of this batch's graph
 	virtual int addToPileup(GaBackendPileup*, const GaPileupAdd&, GaPileupAddOut&) { return 100; }

@@ -253,6 +253,28 @@ void hostSlots(const ga_graph& g, const Trace& bw, const Trace& fw, std::vector<
 		}
 }
 
+// the path sequence of a read from its parts' cells and its TraceItem list (include/graphaligner_amd.h: GA_F_PATHSEQ): per part the base
+// of its first cell, then the graph_char of every item of type MATCH, MISMATCH or DELETION; cells on a dummy node give nothing
+void hostPathBases(const ga_graph& g, const Trace& bw, const Trace& fw, const std::vector<ga_trace_item_t>& items, std::vector<char>& into, uint32_t& nBackward)
+{
+	into.clear();
+	nBackward = 0;
+	size_t at = 0;
+	const uint32_t lastNode = g.nodeCount() - 1;
+	for (const Trace* part : {&bw, &fw})
+	{
+		if (!part->empty() && (*part)[0].node != 0 && (*part)[0].node != lastNode) into.push_back(g.baseChar((*part)[0].node, (*part)[0].offset));
+		for (size_t i = 1; i < part->size() && at < items.size(); i++, at++)
+		{
+			const Pos& p = (*part)[i];
+			const int type = items[at].type;
+			if (p.node == 0 || p.node == lastNode) continue;
+			if (type == 1 || type == 2 || type == 4) into.push_back(items[at].graph_char);
+		}
+		if (part == &bw) { nBackward = (uint32_t)into.size(); if (!bw.empty() && !fw.empty()) at++; }         // (the SPLIT item)
+	}
+}
+
 // a TraceItem list's types cut into maximal runs
 void itemRuns(const std::vector<ga_trace_item_t>& items, std::vector<uint32_t>& into)
 {
@@ -274,6 +296,8 @@ struct alignas(64) Scratch
 	std::vector<uint32_t> opRuns, pileJobs;
 	std::vector<uint64_t> pilePairs, pairsOfRead;
 	std::vector<uint32_t> pileSlots, slotsOfRead;
+	std::vector<char> pathBases;
+	uint32_t pathBackward = 0;
 	std::vector<NodeRun> runs;
 	uint64_t columnUpdates = 0;
 };
@@ -299,7 +323,8 @@ struct Collector
 	const size_t nReads;
 	// GA_F_OPS: every job's runs as the back end coded them (ga_ops.h), in the final order of the job's part of the TraceItem list
 	// GA_F_PILEUP: the same walk on the device later (ga_pileup.h), so the same reads are left to the host's TraceItem list
-	const bool wantTrace, wantOps, wantPile, wantWalk;
+	// GA_F_PATHSEQ: every job's bases as the back end wrote them (ga_pathseq.h), in the final order of the job's part
+	const bool wantTrace, wantOps, wantPile, wantPath, wantWalk;
 	std::unique_ptr<ResultsOwner> R;
 	// the records, moves and runs stay the back end's from fetch until fetchDone
 	struct Fetched { GaBackendBatch* dev = nullptr; void done() { if (dev) dev->fetchDone(); dev = nullptr; } ~Fetched() { done(); } } fetched;
@@ -307,7 +332,8 @@ struct Collector
 	const uint8_t* moves = nullptr;
 	uint64_t nMoveBytes = 0;
 	GaOpsOut devOps;
-	std::vector<uint64_t> mapAt, editAt, traceAt, opsAt;
+	GaPathSeqOut devPath;
+	std::vector<uint64_t> mapAt, editAt, traceAt, opsAt, pathAt;
 	// GA_F_OPS: reads whose runs are derived here from the TraceItem list instead (include/graphaligner_amd.h: GA_F_OPS): a character
 	// outside IUPAC (the item pass decides the read's status), and a forward part that the reference leaves unshifted (:3091-3094)
 	// or whose rows it does not cut at the overlap (the unsigned difference of :3051 wraps) -- there the device's characters are not
@@ -319,14 +345,16 @@ struct Collector
 	ga_trace_item_t* allTrace = nullptr;
 	ga_read_ops_t* allReadOps = nullptr;
 	uint32_t* allOps = nullptr;
+	ga_read_path_seq_t* allReadPath = nullptr;
+	char* allPathBases = nullptr;
 	std::atomic<int> overflow{0};
-	std::atomic<uint64_t> forwardOnlyReads{0}, opsFromDevice{0}, opsFromHost{0}, pileFromDevice{0}, pileFromHost{0};
+	std::atomic<uint64_t> forwardOnlyReads{0}, opsFromDevice{0}, opsFromHost{0}, pileFromDevice{0}, pileFromHost{0}, pathFromDevice{0}, pathFromHost{0};
 	std::chrono::steady_clock::time_point t0, t1, t2;
 	size_t nThreads = 1;
 
 	explicit Collector(ga_batch* batch)
 		: b(batch), g(*batch->g), nReads(batch->reads.size()), wantTrace((batch->flags & GA_F_TRACE) != 0), wantOps((batch->flags & GA_F_OPS) != 0),
-		  wantPile((batch->flags & GA_F_PILEUP) != 0), wantWalk(wantOps || wantPile) {}
+		  wantPile((batch->flags & GA_F_PILEUP) != 0), wantPath((batch->flags & GA_F_PATHSEQ) != 0), wantWalk(wantOps || wantPile || wantPath) {}
 
 	int fetch();
 	int sizePlaces();
@@ -340,8 +368,10 @@ struct Collector
 	bool forwardOnly(size_t ri, ga_read_result_t& rr, Scratch& s);
 	int seedTraces(const SeedPlan& sp, const ReadSeq& seq, BestSeed& cur);
 	int bestSeed(size_t ri, ga_read_result_t& rr, BestSeed& best);
-	bool derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOps, bool& hostPile);
-	void store(size_t ri, ga_read_result_t& rr, const BestSeed& best, Scratch& s, bool hostOps, bool hostPile);
+	bool derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOps, bool& hostPile, bool& hostPath);
+	void store(size_t ri, ga_read_result_t& rr, const BestSeed& best, Scratch& s, bool hostOps, bool hostPile, bool hostPath);
+	void devicePath(int64_t bwJob, bool bwCells, int64_t fwJob, bool fwCells, std::vector<char>& into, uint32_t& nBackward) const;
+	bool storePath(size_t ri, const std::vector<char>& basesOfRead, uint32_t nBackward, bool fromHost);
 	void deviceOps(int64_t bwJob, bool bwCells, int64_t fwJob, bool fwCells, std::vector<uint32_t>& into) const;
 	bool storeOps(size_t ri, const std::vector<uint32_t>& runsOfRead, bool fromHost);
 	void fail(ga_read_result_t& rr) { overflow.store(1); rr.status = GA_E_DEVICE; }   // (a bound of sizePlaces is wrong: fail loudly instead of writing past a read's place)
@@ -360,6 +390,11 @@ int Collector::fetch()
 		if (int s = b->dev->fetchOps(devOps)) return s;
 		if (!outs.empty() && (!devOps.runs || !devOps.offsets)) return GA_E_DEVICE;
 	}
+	if (wantPath)
+	{
+		if (int s = b->dev->fetchPathSeq(devPath)) return s;
+		if (!outs.empty() && (!devPath.bases || !devPath.offsets)) return GA_E_DEVICE;
+	}
 	t1 = std::chrono::steady_clock::now();
 	b->columnUpdates = 0;
 	b->slicesRun = 0;
@@ -372,11 +407,12 @@ int Collector::sizePlaces()
 {
 	R.reset(new ResultsOwner());
 	mapAt.assign(nReads + 1, 0); editAt.assign(nReads + 1, 0); traceAt.assign(nReads + 1, 0); opsAt.assign(wantOps ? nReads + 1 : 0, 0);
+	pathAt.assign(wantPath ? nReads + 1 : 0, 0);
 	opsOnHost.assign(wantWalk ? nReads : 0, 0);
 	for (size_t ri = 0; ri < nReads; ri++)
 	{
 		const ReadPlan& rp = b->reads[ri];
-		uint64_t runs = 1, items = 0, opRuns = 0;
+		uint64_t runs = 1, items = 0, opRuns = 0, bases = 0;
 		for (size_t k = rp.firstSeed; k < rp.firstSeed + rp.nSeeds; k++)
 		{
 			const SeedPlan& sp = b->seeds[k];
@@ -385,6 +421,7 @@ int Collector::sizePlaces()
 				{
 					runs += (uint64_t)outs[job].n_node_steps + 1; items += (uint64_t)outs[job].trace_len + 2;
 					if (wantOps) opRuns += devOps.offsets[job + 1] - devOps.offsets[job] + 1;
+					if (wantPath) bases += devPath.offsets[job + 1] - devPath.offsets[job];
 				}
 			if (wantWalk)
 			{
@@ -397,6 +434,14 @@ int Collector::sizePlaces()
 		traceAt[ri + 1] = traceAt[ri] + (wantTrace ? items : 0);
 		if (wantWalk && b->readInvalid[ri].load(std::memory_order_relaxed)) opsOnHost[ri] = 1;
 		if (wantOps) opsAt[ri + 1] = opsAt[ri] + (opsOnHost[ri] ? items : opRuns);
+		// (a part of K cells has at most K bases, and a job's cells are its moves + 1)
+		if (wantPath) pathAt[ri + 1] = pathAt[ri] + (opsOnHost[ri] ? items : bases);
+	}
+	if (wantPath)
+	{
+		allReadPath = (ga_read_path_seq_t*)R->allReadPath.get((nReads + 1) * sizeof(ga_read_path_seq_t));
+		allPathBases = (char*)R->allPathBases.get(pathAt[nReads] + 1);
+		if (!allReadPath || !allPathBases) return GA_E_INVALID;
 	}
 	if (wantOps)
 	{
@@ -521,6 +566,27 @@ void Collector::deviceOps(int64_t bwJob, bool bwCells, int64_t fwJob, bool fwCel
 	if (fwCells && fwJob >= 0) into.insert(into.end(), devOps.runs + devOps.offsets[fwJob], devOps.runs + devOps.offsets[fwJob + 1]);
 }
 
+// the winning seed's bases: backward job, forward job
+void Collector::devicePath(int64_t bwJob, bool bwCells, int64_t fwJob, bool fwCells, std::vector<char>& into, uint32_t& nBackward) const
+{
+	into.clear();
+	if (bwCells && bwJob >= 0) into.insert(into.end(), devPath.bases + devPath.offsets[bwJob], devPath.bases + devPath.offsets[bwJob + 1]);
+	nBackward = (uint32_t)into.size();
+	if (fwCells && fwJob >= 0) into.insert(into.end(), devPath.bases + devPath.offsets[fwJob], devPath.bases + devPath.offsets[fwJob + 1]);
+}
+
+// a read's finished bases into its place
+bool Collector::storePath(size_t ri, const std::vector<char>& basesOfRead, uint32_t nBackward, bool fromHost)
+{
+	if (basesOfRead.size() > pathAt[ri + 1] - pathAt[ri]) return false;
+	ga_read_path_seq_t& rp = allReadPath[ri];
+	rp.n_bases = (uint32_t)basesOfRead.size();
+	rp.n_backward = nBackward;
+	if (!basesOfRead.empty()) memcpy(allPathBases + pathAt[ri], basesOfRead.data(), basesOfRead.size());
+	if (!fromHost) pathFromDevice++;                        // (a read on the host path was counted when its item pass ran)
+	return true;
+}
+
 // a read's finished runs into its place, with the four counts
 bool Collector::storeOps(size_t ri, const std::vector<uint32_t>& runsOfRead, bool fromHost)
 {
@@ -562,6 +628,15 @@ bool Collector::forwardOnly(size_t ri, ga_read_result_t& rr, Scratch& s)
 		if (!storeOps(ri, s.opRuns, false)) { fail(rr); return true; }
 	}
 	if (wantPile) { s.pileJobs.push_back((uint32_t)sp.fwJob | GA_PILEUP_COUNTS); pileFromDevice++; }
+	if (wantPath)
+	{
+		// the device bytes of the one job, as they are
+		const uint64_t from = devPath.offsets[sp.fwJob], n = devPath.offsets[sp.fwJob + 1] - from;
+		if (n > pathAt[ri + 1] - pathAt[ri]) { fail(rr); return true; }
+		if (n) memcpy(allPathBases + pathAt[ri], devPath.bases + from, n);
+		allReadPath[ri].n_bases = (uint32_t)n;
+		pathFromDevice++;
+	}
 	rr.failed = 0;
 	rr.score = o.score;
 	rr.n_mappings = s.runs.size();
@@ -642,7 +717,7 @@ int Collector::bestSeed(size_t ri, ga_read_result_t& rr, BestSeed& best)
 
 // What is derived from the kept seed's cells: the TraceItem list (s.items; left empty unless GA_F_TRACE wants it) and, for the reads
 // left to the host, the runs of GA_F_OPS (s.opRuns) and the items of GA_F_PILEUP (s.pairsOfRead).  False where the reference asserts.
-bool Collector::derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOps, bool& hostPile)
+bool Collector::derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOps, bool& hostPile, bool& hostPath)
 {
 	const ReadSeq& seq = b->seqs[ri];
 	// the reference always builds the TraceItem list (:463) and characterMatch asserts on a
@@ -654,9 +729,12 @@ bool Collector::derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOp
 	// by this scan; the device's runs of such a read are within the bound its place was sized with, and storeOps checks it)
 	hostOps = wantOps && (opsOnHost[ri] || suspicious);
 	hostPile = wantPile && (opsOnHost[ri] || suspicious);
-	if (!(wantTrace || suspicious || hostOps || hostPile)) return true;
+	hostPath = wantPath && (opsOnHost[ri] || suspicious);
+	if (!(wantTrace || suspicious || hostOps || hostPile || hostPath)) return true;
 	const bool fine = traceItems(g, seq, best.bw, best.fw, s.items);
 	if (hostOps) opsFromHost++;
+	if (hostPath) pathFromHost++;
+	if (hostPath && fine) hostPathBases(g, best.bw, best.fw, s.items, s.pathBases, s.pathBackward);
 	if (hostPile && fine) { hostPairs(g, best.bw, best.fw, s.items, s.pairsOfRead); hostSlots(g, best.bw, best.fw, s.slotsOfRead); }
 	if (hostOps && fine) itemRuns(s.items, s.opRuns);
 	if (!wantTrace || !fine) s.items.clear();
@@ -664,7 +742,7 @@ bool Collector::derive(size_t ri, const BestSeed& best, Scratch& s, bool& hostOp
 }
 
 // the kept seed's mappings (traceToAlignment of both parts, merged), runs, pileup entries and trace items into the read's place
-void Collector::store(size_t ri, ga_read_result_t& rr, const BestSeed& best, Scratch& s, bool hostOps, bool hostPile)
+void Collector::store(size_t ri, ga_read_result_t& rr, const BestSeed& best, Scratch& s, bool hostOps, bool hostPile, bool hostPath)
 {
 	const ReadSeq& seq = b->seqs[ri];
 	Partial fwp = toMappings(g, seq, best.fwScore, best.fw);
@@ -678,6 +756,11 @@ void Collector::store(size_t ri, ga_read_result_t& rr, const BestSeed& best, Scr
 	{
 		if (!hostOps) deviceOps(best.bwJob, !best.bw.empty(), best.fwJob, !best.fw.empty(), s.opRuns);
 		if (!storeOps(ri, s.opRuns, hostOps)) { fail(rr); return; }
+	}
+	if (wantPath)
+	{
+		if (!hostPath) devicePath(best.bwJob, !best.bw.empty(), best.fwJob, !best.fw.empty(), s.pathBases, s.pathBackward);
+		if (!storePath(ri, s.pathBases, s.pathBackward, hostPath)) { fail(rr); return; }
 	}
 	if (wantPile)
 	{
@@ -722,15 +805,16 @@ void Collector::work(size_t lo, size_t hi, Scratch& s)
 		rr.first_mapping = mapAt[ri];
 		rr.first_trace = traceAt[ri];
 		if (wantOps) { memset(&allReadOps[ri], 0, sizeof(ga_read_ops_t)); allReadOps[ri].first_op = opsAt[ri]; }
+		if (wantPath) { memset(&allReadPath[ri], 0, sizeof(ga_read_path_seq_t)); allReadPath[ri].first_base = pathAt[ri]; }
 		if (b->reads[ri].nSeeds == 0) { rr.status = GA_S_ASSERTION; continue; }          // assert(seedHits.size() > 0) (:412)
 		if (forwardOnly(ri, rr, s)) { s.columnUpdates += rr.column_updates; forwardOnlyReads++; continue; }
 		BestSeed best;
 		rr.status = bestSeed(ri, rr, best);
 		s.columnUpdates += rr.column_updates;
 		if (rr.status != GA_S_OK || !best.have) continue;
-		bool hostOps = false, hostPile = false;
-		if (!derive(ri, best, s, hostOps, hostPile)) { rr.status = GA_S_ASSERTION; continue; }
-		store(ri, rr, best, s, hostOps, hostPile);
+		bool hostOps = false, hostPile = false, hostPath = false;
+		if (!derive(ri, best, s, hostOps, hostPile, hostPath)) { rr.status = GA_S_ASSERTION; continue; }
+		store(ri, rr, best, s, hostOps, hostPile, hostPath);
 	}
 }
 
@@ -749,6 +833,7 @@ void Collector::assemble()
 		b->pileSlots.insert(b->pileSlots.end(), scratch[t].pileSlots.begin(), scratch[t].pileSlots.end());
 	}
 	b->opsFromDevice = opsFromDevice.load(); b->opsFromHost = opsFromHost.load();
+	b->pathFromDevice = pathFromDevice.load(); b->pathFromHost = pathFromHost.load();
 	fetched.done();
 	t2 = std::chrono::steady_clock::now();
 }
@@ -773,6 +858,7 @@ int Collector::publish(ga_results_t** out)
 	pub.n_edit_bytes = b->seqBufBytes; pub.edit_bytes = allEdits;
 	pub.n_trace = traceAt[nReads]; pub.trace = allTrace;
 	pub.read_ops = allReadOps; pub.n_ops = wantOps ? opsAt[nReads] : 0; pub.ops = allOps;
+	pub.read_path_seq = allReadPath; pub.n_path_bases = wantPath ? pathAt[nReads] : 0; pub.path_bases = allPathBases;
 	*out = &R.release()->pub;
 	if (getenv("GA_DEBUG_COLLECT"))
 	{
@@ -828,6 +914,20 @@ int ga_batch_ops_stats(const ga_batch_t* b, ga_batch_ops_stats_t* out)
 		out->jobs_coded = o.jobs; out->moves_read = o.moves; out->runs_written = o.n_runs;
 	}
 	out->reads_from_device = b->opsFromDevice; out->reads_from_host = b->opsFromHost;
+	return GA_S_OK;
+}
+
+int ga_batch_path_seq_stats(const ga_batch_t* b, ga_batch_path_seq_stats_t* out)
+{
+	if (!b || !out || !b->dev || !(b->flags & GA_F_PATHSEQ)) return GA_E_INVALID;
+	memset(out, 0, sizeof(*out));
+	GaPathSeqOut o;
+	if (b->ran && b->dev->fetchPathSeq(o) == 0)
+	{
+		out->count_kernel_ms = o.count_ms; out->write_kernel_ms = o.write_ms;
+		out->jobs_walked = o.jobs; out->moves_read = o.moves; out->bases_written = o.n_bases;
+	}
+	out->reads_from_device = b->pathFromDevice; out->reads_from_host = b->pathFromHost;
 	return GA_S_OK;
 }
 
@@ -912,12 +1012,22 @@ int ga_results_unsplit(const ga_graph_t* g, const ga_results_t* in, ga_results_t
 			R->ops.insert(R->ops.end(), in->ops + from, in->ops + from + ro.n_ops);
 			R->readOps.push_back(ro);
 		}
+		if (in->read_path_seq)
+		{
+			// (so do the bases: cutting nodes into pieces does not change them)
+			ga_read_path_seq_t rp = in->read_path_seq[i];
+			const uint64_t from = rp.first_base;
+			rp.first_base = R->pathBases.size();
+			R->pathBases.insert(R->pathBases.end(), in->path_bases + from, in->path_bases + from + rp.n_bases);
+			R->readPath.push_back(rp);
+		}
 	}
 	R->pub.n_reads = R->reads.size(); R->pub.reads = R->reads.data();
 	R->pub.n_mappings = R->mappings.size(); R->pub.mappings = R->mappings.data();
 	R->pub.n_edit_bytes = R->edits.size(); R->pub.edit_bytes = R->edits.data();
 	R->pub.n_trace = R->trace.size(); R->pub.trace = R->trace.data();
 	if (in->read_ops) { R->pub.read_ops = R->readOps.data(); R->pub.n_ops = R->ops.size(); R->pub.ops = R->ops.data(); }
+	if (in->read_path_seq) { R->pub.read_path_seq = R->readPath.data(); R->pub.n_path_bases = R->pathBases.size(); R->pub.path_bases = R->pathBases.data(); }
 	*out = &R->pub;
 	return GA_S_OK;
 }

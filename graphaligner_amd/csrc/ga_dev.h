@@ -151,6 +151,7 @@ struct DevGraph : GaBackendGraph
 	bool buildsMatchWords() const override { return true; }
 	bool codesOps() const override { return true; }
 	bool codesPileup() const override { return true; }
+	bool writesPathSeq() const override { return true; }
 	GaBackendPileup* createPileup(const GaPileupSpec& spec, int* status) override
 	{
 		*status = GA_E_INVALID;

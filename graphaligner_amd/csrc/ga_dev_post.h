@@ -1,6 +1,6 @@
 // ga_dev_post.h -- what follows the ladder: the walk over the finished jobs' moves where they lie in the trace pool, coding them as runs
-// of operations (GA_F_OPS, ga_ops.h) or adding them to a pileup (GA_F_PILEUP, ga_pileup.h, ga_edges.h); a pileup's site queries
-// (ga_sites.h); and the records and moves on their way back to the host (fetch).
+// of operations (GA_F_OPS, ga_ops.h), spelling out the graph's bases along them (GA_F_PATHSEQ, ga_pathseq.h) or adding them to a pileup
+// (GA_F_PILEUP, ga_pileup.h, ga_edges.h); a pileup's site queries (ga_sites.h); and the records and moves on their way back to the host (fetch).
 // Not a header for others: a part of ga_device.hip's translation unit (ga_dev.h).
 #ifndef GA_DEVICE_PARTS
 #error "ga_dev_post.h is a part of ga_device.hip"
@@ -23,6 +23,16 @@ struct DevBatch final : BatchLadder
 		std::vector<uint64_t> offsetsHost;
 		std::unique_ptr<uint32_t[]> runsHost;
 	} ops;
+	struct PathSeq
+	{
+		Events<4> ev;                   // around count, around write
+		uint64_t* dOffsets = nullptr;   // device copies, until fetch has brought them down
+		uint8_t* dBases = nullptr;
+		uint64_t total = 0, jobs = 0, moves = 0;
+		float countMs = 0, writeMs = 0;
+		std::vector<uint64_t> offsetsHost;
+		std::unique_ptr<uint8_t[]> basesHost;
+	} pathSeq;
 	struct PileupAdd { Events<2> ev; } pileupAdd;
 	struct HostTraces
 	{
@@ -35,12 +45,24 @@ struct DevBatch final : BatchLadder
 	int run() override
 	{
 		int rc = runLadder();
-		if (rc || !cfg.emit_ops) return rc;
-		releaseOps();
-		ops.total = ops.jobs = ops.moves = 0; ops.countMs = ops.writeMs = 0;
-		ops.offsetsHost.clear(); ops.runsHost.reset();
-		if (jobs.empty()) { ops.offsetsHost.assign(1, 0); ops.runsHost.reset(new uint32_t[1]); return 0; }
-		return runOps();
+		if (rc) return rc;
+		if (cfg.emit_ops)
+		{
+			releaseOps();
+			ops.total = ops.jobs = ops.moves = 0; ops.countMs = ops.writeMs = 0;
+			ops.offsetsHost.clear(); ops.runsHost.reset();
+			if (jobs.empty()) { ops.offsetsHost.assign(1, 0); ops.runsHost.reset(new uint32_t[1]); }
+			else if (int s = runOps()) return s;
+		}
+		if (cfg.emit_pathseq)
+		{
+			releasePathSeq();
+			pathSeq.total = pathSeq.jobs = pathSeq.moves = 0; pathSeq.countMs = pathSeq.writeMs = 0;
+			pathSeq.offsetsHost.clear(); pathSeq.basesHost.reset();
+			if (jobs.empty()) { pathSeq.offsetsHost.assign(1, 0); pathSeq.basesHost.reset(new uint8_t[1]); }
+			else if (int s = runPathSeq()) return s;
+		}
+		return 0;
 	}
 
 	// ---- the walk (ga_ops.h: run_wave and its callers): one wave per job at a time, over `n` jobs ------------------------------------
@@ -115,6 +137,62 @@ struct DevBatch final : BatchLadder
 		if (!cfg.emit_ops) return GA_E_INVALID;
 		out.runs = ops.runsHost.get(); out.offsets = ops.offsetsHost.empty() ? nullptr : ops.offsetsHost.data();
 		out.n_runs = ops.total; out.count_ms = ops.countMs; out.write_ms = ops.writeMs; out.jobs = ops.jobs; out.moves = ops.moves;
+		return 0;
+	}
+
+	// ---- GA_F_PATHSEQ (ga_pathseq.h): after the last pass (and the operations), every finished job's bases along its moves ----------
+	void releasePathSeq()
+	{
+		if (pathSeq.dOffsets) blocks.release(pathSeq.dOffsets);
+		if (pathSeq.dBases) blocks.release(pathSeq.dBases);
+		pathSeq.dOffsets = nullptr; pathSeq.dBases = nullptr;
+	}
+	int runPathSeq()
+	{
+		if (!res.fills) return GA_E_INVALID;
+		const size_t n = jobs.size();
+		uint64_t* dCounts; uint8_t* dTmp;
+		if (alloc(&dCounts, n + 1) || alloc(&pathSeq.dOffsets, n + 1)) return GA_E_DEVICE;
+		Scan<uint64_t> place{dCounts, pathSeq.dOffsets, n + 1};
+		if (int s = place.size(stream)) return s;
+		if (alloc(&dTmp, place.tmpBytes + 16)) return GA_E_DEVICE;
+		if (int s = pathSeq.ev.create()) return s;
+		HIP_OK(hipMemsetAsync(dCounts, 0, (n + 1) * 8, stream));
+		if (uploadList(orderHost)) return GA_E_DEVICE;           // longest first, dealt statically, as the operations are
+		gaps::PathLaunch P;
+		memset(&P, 0, sizeof(P));
+		P.walk = walkLaunch(nullptr, twinTable());               // (no read character is looked at: no row codes)
+		if (!P.walk.twin) return GA_E_INVALID;
+		P.walk.job_list = dList;
+		P.walk.counts = dCounts; P.walk.offsets = pathSeq.dOffsets;
+		const uint32_t waves = walkWaves(n);
+		HIP_OK(hipEventRecord(pathSeq.ev[0], stream));
+		hipLaunchKernelGGL(ga_pathseq_count_kernel, dim3(waves), dim3(64), 0, stream, P);
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipEventRecord(pathSeq.ev[1], stream));
+		if (int s = place.run(dTmp, stream)) return s;
+		HIP_OK(hipMemcpyAsync(&pathSeq.total, pathSeq.dOffsets + n, 8, hipMemcpyDeviceToHost, stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		if (alloc(&pathSeq.dBases, pathSeq.total + 1)) return GA_E_DEVICE;
+		P.bases = pathSeq.dBases;
+		HIP_OK(hipEventRecord(pathSeq.ev[2], stream));
+		hipLaunchKernelGGL(ga_pathseq_write_kernel, dim3(waves), dim3(64), 0, stream, P);
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipEventRecord(pathSeq.ev[3], stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		if (pathSeq.ev.elapsed(0, 1, pathSeq.countMs) || pathSeq.ev.elapsed(2, 3, pathSeq.writeMs)) return GA_E_DEVICE;
+		blocks.release(dCounts); blocks.release(dTmp);
+		pathSeq.jobs = pathSeq.moves = 0;
+		for (const GaJobOut& o : outs) if (movesCount(o)) { pathSeq.jobs++; pathSeq.moves += o.trace_len; }
+		if (knobs.debugPasses) fprintf(stderr, "graphaligner_amd: path sequences: %llu jobs, %llu moves, %llu bases on %u waves, count %.2f ms, write %.2f ms\n",
+		                               (unsigned long long)pathSeq.jobs, (unsigned long long)pathSeq.moves, (unsigned long long)pathSeq.total, waves, pathSeq.countMs, pathSeq.writeMs);
+		return 0;
+	}
+	int fetchPathSeq(GaPathSeqOut& out) override
+	{
+		if (!cfg.emit_pathseq) return GA_E_INVALID;
+		out.bases = pathSeq.basesHost.get(); out.offsets = pathSeq.offsetsHost.empty() ? nullptr : pathSeq.offsetsHost.data();
+		out.n_bases = pathSeq.total; out.count_ms = pathSeq.countMs; out.write_ms = pathSeq.writeMs; out.jobs = pathSeq.jobs; out.moves = pathSeq.moves;
 		return 0;
 	}
 
@@ -256,6 +334,16 @@ struct DevBatch final : BatchLadder
 			if (ops.total) HIP_OK(hipMemcpyAsync(ops.runsHost.get(), ops.dRuns, ops.total * 4, hipMemcpyDeviceToHost, stream));
 			HIP_OK(hipStreamSynchronize(stream));
 			releaseOps();
+		}
+		if (cfg.emit_pathseq && pathSeq.dOffsets)
+		{
+			// ... and so do the bases and theirs
+			pathSeq.offsetsHost.resize(jobs.size() + 1);
+			pathSeq.basesHost.reset(new uint8_t[pathSeq.total + 1]);
+			HIP_OK(hipMemcpyAsync(pathSeq.offsetsHost.data(), pathSeq.dOffsets, pathSeq.offsetsHost.size() * 8, hipMemcpyDeviceToHost, stream));
+			if (pathSeq.total) HIP_OK(hipMemcpyAsync(pathSeq.basesHost.get(), pathSeq.dBases, pathSeq.total, hipMemcpyDeviceToHost, stream));
+			HIP_OK(hipStreamSynchronize(stream));
+			releasePathSeq();
 		}
 		return 0;
 	}

@@ -70,7 +70,7 @@ struct BatchPrepared : BatchCore
 			HIP_OK(hipMemsetAsync(dRows + rowBytes - 128, 0, 128, stream));
 			res.rows = dRows;
 			res.seq = dSeq; res.seqBytes = src->seqBytes; res.fills = dFills;
-			if ((cfg.emit_ops || cfg.emit_pileup) && src->twin)
+			if ((cfg.emit_ops || cfg.emit_pileup || cfg.emit_pathseq) && src->twin)
 			{
 				// (the twin table alone: a seeded prepare's dTwin serves as well)
 				std::lock_guard<std::mutex> guard(g->twinLock);

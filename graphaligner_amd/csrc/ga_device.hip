@@ -2,8 +2,8 @@
 // each device program -- the extension program one wave per read (ga_kernel.h, which brings ga_sparse.h and ga_job.h with run_job;
 // the three wrappers build their Slot with makeSlot; state in LDS, or in HBM for bands of up to 4 096 nodes,
 // with or without the sparse method) and one lane per read (ga_lanes.h), the match words, the job plan of seeded batches (ga_plan.h),
-// the walk over finished jobs' moves as operations, pileups and edge support (ga_ops.h, ga_pileup.h, ga_edges.h) and the site queries
-// (ga_sites.h); seeding brings its own (ga_seed_dev.h).  The extension kernels are persistent launches: a wave per scratch slot in HBM,
+// the walk over finished jobs' moves as operations, pileups, edge support and path sequences (ga_ops.h, ga_pileup.h, ga_edges.h,
+// ga_pathseq.h) and the site queries (ga_sites.h); seeding brings its own (ga_seed_dev.h).  The extension kernels are persistent launches: a wave per scratch slot in HBM,
 // pulling jobs from a device-side queue; waves share nothing but the queue counter and the trace pool's bump counter.
 // Below the kernels the host side is included in parts, and the entry points of ga_backend.h end the file:
 //   ga_dev.h          the graph resident in HBM with its pools and block list, the pileup, the owners of events, streams, blocks and
@@ -12,7 +12,7 @@
 //                     (included by ga_dev.h between its owners, which the engine uses, and the graph, which holds the engine)
 //   ga_dev_prepare.h  a batch's prepare: reads, jobs and match words into device memory; the seeded prepare (BatchPrepared)
 //   ga_dev_ladder.h   a batch's run: the scratch geometry and the passes of the ladder, ga_ladder.h (BatchLadder)
-//   ga_dev_post.h     after the ladder: operations, pileup add, the results' way back (DevBatch); a pileup's site queries
+//   ga_dev_post.h     after the ladder: operations, path sequences, pileup add, the results' way back (DevBatch); a pileup's site queries
 // A batch is built in these layers, each derived from the one before with its state next to its functions.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -37,6 +37,7 @@
 #include "ga_ops.h"
 #include "ga_pileup.h"
 #include "ga_edges.h"
+#include "ga_pathseq.h"
 #include "ga_sites.h"
 
 namespace {
@@ -354,6 +355,18 @@ __global__ void __launch_bounds__(256) ga_pileup_slots_kernel(const uint32_t* sl
 {
 	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
 	if (i < n) gaed::add_slot(slots, i, counts, entries);
+}
+
+// ---- path sequences (ga_pathseq.h): the same walk leaving the graph's base per visited column, counting and writing ---------------
+__global__ void __launch_bounds__(64) ga_pathseq_count_kernel(gaps::PathLaunch P)
+{
+	__shared__ gao::OpsLds lds;
+	gaps::run_wave<false>(P, lds, blockIdx.x, gridDim.x);
+}
+__global__ void __launch_bounds__(64) ga_pathseq_write_kernel(gaps::PathLaunch P)
+{
+	__shared__ gao::OpsLds lds;
+	gaps::run_wave<true>(P, lds, blockIdx.x, gridDim.x);
 }
 
 // ---- site queries (ga_sites.h): one streaming pass over a pileup's planes marks the sites, a scan places them, a second pass writes them ----

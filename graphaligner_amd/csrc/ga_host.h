@@ -170,8 +170,10 @@ struct ResultsOwner
 	std::vector<ga_trace_item_t> trace;
 	std::vector<ga_read_ops_t> readOps;
 	std::vector<uint32_t> ops;
+	std::vector<ga_read_path_seq_t> readPath;
+	std::vector<char> pathBases;
 	// the arrays of a whole batch (hundreds of MB, not cleared first): from the process-wide pool above, back to it with the results
-	PooledBuffer allReads, allMappings, allTrace, allReadOps, allOps;
+	PooledBuffer allReads, allMappings, allTrace, allReadOps, allOps, allReadPath, allPathBases;
 	std::shared_ptr<char> seqKeep;        // edit_bytes of a batch's results = the batch's copy of the reads, kept alive here
 };
 
@@ -270,6 +272,8 @@ struct ga_batch
 	double seedMs = 0, planMs = 0, eqMs = 0, hostMs = 0;
 	// GA_F_OPS: where the runs of the last collect's aligned reads came from
 	uint64_t opsFromDevice = 0, opsFromHost = 0;
+	// GA_F_PATHSEQ: ... and the bases
+	uint64_t pathFromDevice = 0, pathFromHost = 0;
 	// GA_F_PILEUP: what the last collect left for ga_batch_pileup_add (valid while `collected`): the winning jobs of the aligned reads
 	// (job | 0x80000000, longest first), the items of the reads the host derives them for as (plane << 56 | column), and the two read counts
 	bool collected = false;

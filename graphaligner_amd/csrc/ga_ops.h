@@ -107,7 +107,10 @@ GAO_FN bool self_loop(const GaDevGraph& g, uint32_t node)
 // item with its column to `sink` (ga_pileup.h), which then sees the left moves' cells too and no runs are formed
 // SINK_EDGES (ga_edges.h): the items themselves are not looked at; every node crossing whose two cells both have an item is handed to
 // `sink` as the slot of the edge it takes (position in the in-neighbour lists laid end to end).  Its code is compiled into no other walk
-enum { SINK_COUNT = 0, SINK_WRITE = 1, SINK_ADD = 2, SINK_EDGES = 3 };
+// SINK_PATH (ga_pathseq.h): no item is formed and no read character looked at; every round, with its cells, is handed to `sink`, which
+// counts or writes the cells' bases, and so is the stream's last cell behind the loop (a job without moves still has that cell).  Its
+// code is compiled into no other walk either
+enum { SINK_COUNT = 0, SINK_WRITE = 1, SINK_ADD = 2, SINK_EDGES = 3, SINK_PATH = 4 };
 struct NoSink { GAO_FN void item(uint32_t, uint64_t, uint32_t) {} };
 
 // the runs of one job: returns their number (SINK_ADD: 0)
@@ -117,7 +120,7 @@ template <int SINK, class Sink> GAO_FN uint32_t walk_job(const OpsLaunch& L, Ops
 	const GaDevGraph& G = L.graph;
 	const GaJobOut* o = L.outs + job;
 	const uint32_t nMoves = o->trace_len;
-	if (o->status != GA_OK || o->n_valid == 0 || o->reserved3 == 1 || nMoves == 0) return 0;
+	if (o->status != GA_OK || o->n_valid == 0 || o->reserved3 == 1 || (nMoves == 0 && SINK != SINK_PATH)) return 0;
 	const uint64_t traceOff = o->trace_off;
 	if (traceOff + nMoves > L.trace_bytes || o->start_node >= G.n_nodes) return 0;
 	const uint8_t* mv = L.traces + traceOff;
@@ -210,6 +213,12 @@ template <int SINK, class Sink> GAO_FN uint32_t walk_job(const OpsLaunch& L, Ops
 				}
 			}
 			prevRow = row0 - ((lds.incl[63] - lds.own[63]) & 0xffffu);
+			top -= totalCols; row0 -= totalRows;
+			continue;
+		}
+		if constexpr (SINK == SINK_PATH)
+		{
+			sink.round(L, lds, nValid, row0, traceRows, totalBp);
 			top -= totalCols; row0 -= totalRows;
 			continue;
 		}
@@ -313,6 +322,7 @@ template <int SINK, class Sink> GAO_FN uint32_t walk_job(const OpsLaunch& L, Ops
 		row0 -= totalRows;
 	}
 	if (bad) return 0;
+	if constexpr (SINK == SINK_PATH) return sink.end(L, node, len, col0, top, row0, traceRows, totalBp);
 	if (WRITE && carryType)
 	{
 		GAO_LANES(l)

@@ -80,12 +80,13 @@ static void decideRuns(ga_batch* b)
 	const double meanNode = g->nodeCount() > 2 ? (double)g->bases.size() / (double)(g->nodeCount() - 2) : 64.0;
 	// (with the words built by the back end, whether a row is such a character is known when the batch has been created: the back
 	// end clears the flag then)
-	bool runs = (b->flags & (GA_F_TRACE | GA_F_OPS | GA_F_PILEUP)) == 0 && b->anyInvalidRow.load() == 0 && meanNode >= 40 && !(getenv("GA_RUNS") && atoi(getenv("GA_RUNS")) == 0);
+	bool runs = (b->flags & (GA_F_TRACE | GA_F_OPS | GA_F_PILEUP | GA_F_PATHSEQ)) == 0 && b->anyInvalidRow.load() == 0 && meanNode >= 40 && !(getenv("GA_RUNS") && atoi(getenv("GA_RUNS")) == 0);
 	for (size_t i = 0; i < b->reads.size() && runs; i++) if (b->reads[i].nSeeds > 1) runs = false;
 	for (const SeedPlan& sp : b->seeds) if (sp.bwJob >= 0 || (sp.fwJob >= 0 && sp.pos != 0)) { runs = false; break; }
 	b->cfg.emit_runs = runs ? 1u : 0u;
 	b->cfg.emit_ops = (b->flags & GA_F_OPS) ? 1u : 0u;
 	b->cfg.emit_pileup = (b->flags & GA_F_PILEUP) ? 1u : 0u;
+	b->cfg.emit_pathseq = (b->flags & GA_F_PATHSEQ) ? 1u : 0u;
 }
 
 // ---- what the two prepares share ---------------------------------------------------------------
@@ -96,6 +97,7 @@ static int entryStatus(const ga_graph_t* g, const ga_read_t* reads, size_t nRead
 	if (!g->device) return GA_E_NO_DEVICE;
 	if ((flags & GA_F_OPS) && !g->device->codesOps()) return GA_E_INVALID;
 	if ((flags & GA_F_PILEUP) && !g->device->codesPileup()) return GA_E_INVALID;
+	if ((flags & GA_F_PATHSEQ) && !g->device->writesPathSeq()) return GA_E_INVALID;
 	return GA_S_OK;
 }
 

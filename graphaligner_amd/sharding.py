@@ -176,17 +176,18 @@ def align_queued(graph, reads, seeds, bandwidth, ramp=0, flags=0, dist=None, chu
     if gam:
         return b"".join(res for _, res in sorted(mine, key=lambda kr: kr[0]))
     if summary and mine and isinstance(mine[0][1], tuple):
-        # flags with GA_F_OPS: per chunk (records, op counts, runs per read), merged the same way
-        out = np.zeros(len(reads), dtype=mine[0][1][0].dtype)
-        counts = np.zeros((len(reads), 4), dtype=np.int64)
-        runs = [None] * len(reads)
-        for k, (recs, cnt, rr) in mine:
+        # flags with GA_F_OPS or GA_F_PATHSEQ: per chunk (records, then what Batch.collect(summary=True) adds for the flags: arrays with
+        # one row per read, or lists with one entry per read), merged the same way
+        merged = [np.zeros((len(reads),) + part.shape[1:], dtype=part.dtype) if isinstance(part, np.ndarray) else [None] * len(reads) for part in mine[0][1]]
+        for k, parts in mine:
             idx = np.asarray(chunks[k], dtype=np.int64)
-            out[idx] = recs
-            counts[idx] = cnt
-            for i, r in zip(chunks[k], rr):
-                runs[i] = r
-        return out, counts, runs
+            for into, part in zip(merged, parts):
+                if isinstance(part, np.ndarray):
+                    into[idx] = part
+                else:
+                    for i, r in zip(chunks[k], part):
+                        into[i] = r
+        return tuple(merged)
     if summary:
         out = np.zeros(len(reads), dtype=mine[0][1].dtype) if mine else np.zeros(0)
         for k, res in mine:

@@ -157,6 +157,13 @@ typedef struct ga_read_ops {
 #define GA_OP_DELETION 4u
 #define GA_OP_SPLIT 5u
 
+/* per read with GA_F_PATHSEQ: its path sequence is results->path_bases[first_base .. first_base + n_bases), ASCII A, C, G, T, not
+ * terminated; the first n_backward of them are the backward part's (0: the read has no backward part; n_bases: it has no forward part) */
+typedef struct ga_read_path_seq {
+	uint64_t first_base;
+	uint32_t n_bases, n_backward;
+} ga_read_path_seq_t;
+
 /* The three arrays behind `reads` are written by several host threads at places fixed before the lengths are known, so they have GAPS:
  * n_mappings / n_edit_bytes / n_trace are the arrays' extents, not counts of valid entries, and the bytes between one read's entries
  * and the next's are unspecified (recycled memory).  Valid entries are exactly those a read's record points at:
@@ -175,6 +182,11 @@ typedef struct ga_results {
 	const ga_read_ops_t* read_ops;          /* [n_reads] */
 	size_t n_ops;                           /* extent of `ops` */
 	const uint32_t* ops;                    /* a run: bits 0-2 the type, bits 3-31 the length (at least 1) */
+	/* GA_F_PATHSEQ only (all three NULL / 0 without the flag): per read the graph's bases along its alignment; `path_bases` has gaps like
+	 * the arrays above: valid bytes are exactly those a read's record points at */
+	const ga_read_path_seq_t* read_path_seq; /* [n_reads] */
+	size_t n_path_bases;                    /* extent of `path_bases` */
+	const char* path_bases;
 } ga_results_t;
 
 /* ---- alignment ----------------------------------------------------------------------------------------- */
@@ -211,6 +223,35 @@ typedef struct ga_results {
  * part has cells.  Nothing is launched or allocated in ga_batch_run because of the flag, and no result changes.  A back end that cannot
  * add pileups refuses the prepare with GA_E_INVALID. */
 #define GA_F_PILEUP 4u
+/* GA_F_PATHSEQ: PATH SEQUENCES, THE GRAPH'S BASES ALONG EACH ALIGNMENT, WRITTEN ON THE DEVICE (what the reference's ExtractPathSequence
+ * spells out of an alignment's path, and later releases call --corrected-out).  THE RULE.  A read's alignment has up to two parts, the
+ * winning seed's backward part and its forward part.  After reverseTrace each part is a list of cells c_0 .. c_{K-1} in read order with
+ * K - 1 TraceItems, item k describing c_k (getTraceInfoInner, GraphAligner.h:718-780).  The path sequence of a part is the base of c_0,
+ * then the graph_char of every item k >= 1 whose type is MATCH, MISMATCH or DELETION: one base per column the part visits, in read
+ * order.  An INSERTION stays in its column and gives nothing.  A step up inside a node of length 1 that has itself as out-neighbour is a
+ * diagonal to the reference (:742) and gives that base again.  A cell on either dummy node gives nothing.  A backward part's bases are
+ * those of its mirror cells: the other strand's node at the offset counted from its end, read through the graph's mirror table as
+ * GA_F_OPS does (the complement is taken only on a back end that was given no table).  A read's path sequence is the backward part's
+ * bases followed by the forward part's; n_backward says where the one ends.  The SPLIT item gives nothing: its graph_char is the forward
+ * part's c_0, which the forward part already emits.
+ * THE SEAM.  The reference extends the two parts independently from the seed node (getSplitAlignment, :2969-3020), so at the seam the two
+ * pieces may overlap or leave a gap inside that node, exactly as the reference's mappings do.  Nothing is stitched.
+ * A read with failed != 0 or status != GA_S_OK has no sequence (n_bases 0).
+ * What it means per extension job, whose traceback is a stream of moves from its start cell back to row 0 (see GA_F_OPS): cells at rows
+ * >= the job's trace_rows are dropped; a job with no kept cell has no bases.  Forward job: the item describes cell A, where the move
+ * starts; c_0 is the stream's last cell; the bases are stored back to front.  Backward job: the item describes cell B, where the move
+ * leads to; c_0 is the first cell of the stream at a row < trace_rows; the bases are stored in stream order.
+ * Where they are made: by two kernels inside ga_batch_run, after the last pass and after the GA_F_OPS kernels when both flags are set (a
+ * counting launch, the 64-bit scan, a writing launch of one byte per base: no bound, no capacity miss); no read character is looked at.
+ * ga_batch_collect copies the winning seed's bytes.  The reads GA_F_OPS leaves to the host get their bases from the host's cell lists
+ * (ga_batch_path_seq_stats counts them).  Like the other flags it makes the first pass hand back moves, not node runs, and keeps the
+ * mirror table (4 bytes per node) with the graph.  Without the flag nothing changes: no kernel more, no allocation more, no result byte
+ * different.  Limits: one byte per base, some one byte per move of the winning jobs (2-bit packing is not done); a job's count is
+ * 32-bit.  A back end that does not write path sequences refuses the prepare with GA_E_INVALID.
+ * Measured on one MI355X, 50 000 x 10 kb reads (520 M moves, 500 M bases; profiles/path_seq_bench_*.json): the
+ * counting and the writing launch 4.2 and 4.9 ms on the linear graph, 6.1 and 6.9 ms on the bubble graph, each 1.0 to 1.5 ms less than the
+ * GA_F_OPS launch of the same batch; ga_batch_collect 101 ms for the whole batch (500 MB of bases on top of the moves). */
+#define GA_F_PATHSEQ 8u
 int ga_align_batch(const ga_graph_t* g, const ga_read_t* reads, size_t n_reads, const ga_seed_t* seeds, const size_t* seed_offsets,
                    int initial_bandwidth, int ramp_bandwidth, uint32_t flags, ga_results_t** out);
 void ga_results_free(ga_results_t* r);
@@ -261,6 +302,19 @@ typedef struct ga_batch_ops_stats {
 	uint64_t reads_from_host;    /* reads whose runs -- or whose GA_S_ASSERTION -- came from the TraceItem list on the host (see GA_F_OPS) */
 } ga_batch_ops_stats_t;
 int ga_batch_ops_stats(const ga_batch_t* b, ga_batch_ops_stats_t* out);
+
+/* a batch prepared with GA_F_PATHSEQ (GA_E_INVALID otherwise): the two path-sequence kernels of the last ga_batch_run and, from the last
+ * ga_batch_collect, where the reads' bases came from */
+typedef struct ga_batch_path_seq_stats {
+	double count_kernel_ms;      /* HIP-event time of the counting launch */
+	double write_kernel_ms;      /* ... of the writing launch */
+	uint64_t jobs_walked;        /* jobs with status ok, kept slices and move bytes */
+	uint64_t moves_read;         /* their moves */
+	uint64_t bases_written;      /* their bases (all jobs, not the winning seeds' alone) */
+	uint64_t reads_from_device;  /* aligned reads whose bases are the kernels' */
+	uint64_t reads_from_host;    /* reads whose bases -- or whose GA_S_ASSERTION -- came from the cell lists on the host */
+} ga_batch_path_seq_stats_t;
+int ga_batch_path_seq_stats(const ga_batch_t* b, ga_batch_path_seq_stats_t* out);
 
 /* ---- pileups: per-base coverage and allele counts summed on the device -------------------------------- */
 /* THE RULE.  A pileup of kind K over an uploaded graph is K planes of uint32_t, one entry per column of the graph (ga_graph_node_columns:
